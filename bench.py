@@ -6,9 +6,15 @@ batch of B synthetic 3 x 4096 waveforms PLUS one 18-step deterministic Heun samp
 of B waveforms, paper 1-D UNet (BASELINE.json configs[1]); value = N * B / t_step.  Inputs are resident in HBM
 before the timed region.  One process per GPU; for N > 1 launch with torch.distributed.run (RCCL all-reduce).
 
-Also printed in the same JSON line:
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps and prints the JSON line with the headline
+(``value``, ``ms_per_step``) and what the timed steps themselves yield:
   roofline      dominant kernel (fused k=5 conv on bf16x3 MFMA): algorithmic FLOP per launch / HIP-event time per launch
+``--full`` adds everything that takes work of its own after the timed region (each still subject to its ``--no-*`` switch):
+  parity        the same-run parity gate against the CPU oracle
   cpu_baseline  the CPU oracle (a port: our restatement, pinned to the reference by golden vectors) timed on this host
+  parts         the train / sample halves timed separately; the gradient exchange's exposed time (N > 1)
+  kernel_classes, roofline.traffic (live PMC passes), other_configs
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs).
 """
 
 from __future__ import annotations
@@ -595,6 +601,48 @@ def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
 
 
+DUMP_MAX_ELEMS = 1 << 21     # entries per dumped array: a larger output is written as a fixed, seeded sample of this many entries
+DUMP_WEIGHT_ELEMS = 1 << 20  # entries of the updated weights that are written
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _seeded_sample(flat, n, seed):
+    """``flat`` (1-D) itself if it has at most ``n`` entries, else ``n`` of its entries at positions drawn from a CPU generator seeded
+    with ``seed`` (sorted; the same positions in every run with the same sizes)"""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, outs, params=None):
+    """``--dump-outputs``: what the last timed step returned to its caller, written after the timed region as ``path/<name>.npy``
+    (float32 / float64, at most DUMP_MAX_BYTES in all), so that two builds can be compared output for output on identical inputs:
+      sample              the 18-step Heun sample (float64, B x 3 x T)
+      train_loss          the loss the train step returned
+      consistency_sample  --mode consistency: the 1-step sample
+      weights_sample      the parameters after the last timed train step, flattened in ``named_parameters`` order (float32)
+    An array of more than DUMP_MAX_ELEMS entries (DUMP_WEIGHT_ELEMS for the weights) is written flattened, as a fixed seeded sample."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in outs.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        arrays[name] = t if t.numel() <= DUMP_MAX_ELEMS else _seeded_sample(t.reshape(-1), DUMP_MAX_ELEMS, 1)
+    if params is not None:
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        arrays["weights_sample"] = _seeded_sample(flat, DUMP_WEIGHT_ELEMS, 2)
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{k} {a.dtype} {tuple(a.shape)}" for k, a in arrays.items()))
+
+
 def _free_port():
     import socket
     so = socket.socket()
@@ -804,7 +852,17 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the whole sampler integration from one HIP graph (neutral at B=64: GPU-bound)")
     ap.add_argument("--no-auto-graph", dest="auto_graph", action="store_false",
                     help="never graph-replay the sampler (default: the sampler's own choice: eager unless TQDNE_SAMPLER_GRAPH=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline does not need: the same-run parity gate, CPU baselines, the "
+                         "halves timed separately, the gradient-exchange comparison, per-class kernel tables, live PMC passes and the "
+                         "other configurations (each still subject to its --no-* switch); off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (sample, loss, a seeded sample of the updated weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = args.no_tables = args.no_pmc = args.no_other_configs = True
     if args.no_train:
         args.mode = "sample"
     if args.no_sample:
@@ -926,20 +984,22 @@ def main():
 
     def train_half():
         edm.train()
-        trainer.train_step(batch)
+        return trainer.train_step(batch)
 
     def sample_half():
         edm.eval()
-        edm.sample_deterministically(eps0, sigmas, None, cond, use_graph=use_graph)
+        return edm.sample_deterministically(eps0, sigmas, None, cond, use_graph=use_graph)
 
     def one_step():
+        """one step; returns what it handed its caller (device tensors, no synchronisation)"""
         if cm is not None:
-            cm.sample_from(eps32, [], [], None, cond)
-            return
+            return {"consistency_sample": cm.sample_from(eps32, [], [], None, cond)}
+        outs = {}
         if do_train:
-            train_half()
+            outs["train_loss"] = train_half()
         if do_sample:
-            sample_half()
+            outs["sample"] = sample_half()
+        return outs
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -957,7 +1017,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
-        one_step()
+        last_outs = one_step()
         marks[k + 1].record()   # (on the main stream, which every sampler lane / the exchange joins at the end of a step)
     sync()
     dt = time.perf_counter() - t0
@@ -986,6 +1046,9 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     log(f"timed region done: {ms_per_step:.1f} ms/step")
     value = world * B / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outs, list(edm.unet.parameters()) if do_train and cm is None else None)
+    del last_outs
 
     # separate timings of the two halves (reported, not the headline).  `<half>_ms`: 5 calls back to back between two synchronisations,
     # divided by 5 -- the half's throughput time, the way it runs inside the timed steps (no host synchronisation between launches);
@@ -993,7 +1056,7 @@ def main():
     # latency at the start and the drain at the end of every call, ~2 ms for the ~600 launches of a training step)
     parts = {}
     for name, fn in (("train", train_half if do_train else None), ("sample", sample_half if do_sample else None)):
-        if fn is None or cm is not None:
+        if fn is None or cm is not None or not args.full:
             continue
         fn(); sync()
         ts = []
@@ -1014,7 +1077,7 @@ def main():
     exchange = None
     if do_train and cm is None:
         exchange = dict(rccl_ranks=rccl_ranks, overlap=not args.no_overlap, bucket_bytes=4 * getattr(trainer, "bucket_elems", 0))
-        if multi and not args.no_overlap:
+        if multi and not args.no_overlap and args.full:
             def med_train():
                 train_half(); sync()
                 ts = []

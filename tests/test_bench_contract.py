@@ -1,5 +1,6 @@
-"""bench.py's output contract (the driver parses it): ONE JSON line on stdout with the headline fields, the roofline and CPU-baseline
-objects; partial modes are labelled.  Run on the tiny configuration so that it takes seconds."""
+"""bench.py's output contract (the driver parses it): ONE JSON line on stdout with the headline fields; with --full also the CPU-baseline,
+parity, per-part and per-class objects; a plain run does the timed steps only and can dump what they computed; partial modes are
+labelled.  Run on the tiny configuration so that it takes seconds."""
 
 import json
 import os
@@ -24,7 +25,7 @@ def _run(*args, timeout=600, env=None):
 
 @pytest.mark.timeout(900)
 def test_bench_json_contract_tiny_config():
-    d = _run("--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--cpu-batch", "1")
+    d = _run("--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--cpu-batch", "1", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -60,6 +61,32 @@ def test_bench_json_contract_tiny_config():
 
 
 @pytest.mark.timeout(600)
+def test_bench_plain_run_times_the_steps_only_and_dumps_their_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that needs work of its own; --dump-outputs writes what the last
+    timed step returned (float32 / float64, <= 64 MB), and two runs with the same arguments compute the same outputs."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        d = _run("--config", "tiny", "--batch", "4", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / tag))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "waveforms/s"
+        assert abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k in ("cpu_baseline", "parity", "kernel_classes", "other_configs", "train_wf_s", "sample_wf_s"):
+            assert k not in d, k
+        assert d["parts"] == {} and "traffic_counters" not in d["roofline"]
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == ["sample.npy", "train_loss.npy", "weights_sample.npy"], files
+        arrs = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["sample"].shape == (4, 3, 4096) and arrs["sample"].dtype == np.float64
+        runs.append(arrs)
+    for k, a in runs[0].items():
+        b = runs[1][k]
+        assert a.shape == b.shape
+        assert np.abs(a - b).max() <= 1e-5 * max(np.abs(a).max(), 1e-30), k
+
+
+@pytest.mark.timeout(600)
 def test_bench_partial_modes_are_labelled():
     d = _run("--config", "tiny", "--batch", "4", "--steps", "1", "--warmup", "1", "--mode", "sample", "--no-cpu-baseline", "--no-tables")
     assert "DEBUG" in d["metric"] and "cpu_baseline" not in d
@@ -71,7 +98,7 @@ def test_bench_partial_modes_are_labelled():
 def test_bench_runs_the_rccl_path_over_one_rank_when_forced():
     """TQDNE_BENCH_FORCE_RCCL=1: communicator, rank-0 broadcast, bucketed all-reduce issued from inside the backward sweep on RCCL's
     stream, the exchange-after-backward comparison and the checksum gathers all execute on the 1-GPU box (a sum over one rank)."""
-    d = _run("--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-tables",
+    d = _run("--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-tables", "--full",
              env={"TQDNE_BENCH_FORCE_RCCL": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["rccl_forced_at_world1"] is True and d["rccl_ranks"] == 1 and d["rccl_ranks_ok"] is True
     assert d["replicas_equal"] is True and d["replicas"]["weights_moved"] is True
@@ -88,7 +115,7 @@ def test_bench_two_ranks_dry_run_on_one_gpu():
     ranks through torch.distributed.run; with TQDNE_BENCH_BACKEND=gloo + TQDNE_BENCH_SHARE_DEVICE=1 they share cuda:0 and exchange over
     gloo (host staged).  Per-rank shards and seeds, rank-0 broadcast, bucketed exchange issued from inside the backward sweep, the range
     flags in the last bucket, max-over-ranks timing, per-rank times, replica checksums, ONE aggregated JSON line on stdout, exit code 0."""
-    d = _run("--gpus", "2", "--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-tables",
+    d = _run("--gpus", "2", "--config", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-tables", "--full",
              env={"TQDNE_BENCH_BACKEND": "gloo", "TQDNE_BENCH_SHARE_DEVICE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["rccl_ranks_ok"] is True and d["scaling"] == "weak"
     assert "gloo" in d["collective_backend"] and d["shared_device"] is True and "DRY RUN" in d["metric"]

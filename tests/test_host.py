@@ -37,19 +37,26 @@ def test_state_dict_schema_and_layout():
     assert sum(p.numel() for p in t.parameters()) == 3558867
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tqdne"), reason="reference only exists in the build container")
 def test_same_seed_same_weights_as_reference():
-    import sys
-    sys.path.insert(0, "/root/reference")
-    from tqdne.unet import UNetModel as Ref
+    """the reference's state_dict after torch.manual_seed(3), stored as one fingerprint per tensor (tools/make_init_golden.py)"""
+    import hashlib
+
+    import numpy as np
     from tqdne_amd import UNetModel, paper_1d_unet_config
-    cfg = paper_1d_unet_config()
+
+    def fingerprint(t):
+        t = t.detach().cpu().contiguous()
+        h = hashlib.sha256(f"{t.dtype}{tuple(t.shape)}".encode())
+        h.update(t.numpy().tobytes())
+        return h.hexdigest()
+
+    z = np.load(os.path.join(ROOT, "tests", "golden", "paper_init_seed3.npz"), allow_pickle=False)
     torch.manual_seed(3)
-    a = UNetModel(**cfg).state_dict()
-    torch.manual_seed(3)
-    b = Ref(**cfg).state_dict()
-    assert list(a) == list(b)
-    assert all(torch.equal(a[k], b[k]) for k in a)
+    a = UNetModel(**paper_1d_unet_config()).state_dict()
+    assert list(a) == [str(k) for k in z["keys"]]
+    for k, sha, head in zip(z["keys"], z["sha256"], z["head"]):
+        got = a[str(k)].reshape(-1)[:len(head)].double().numpy()
+        assert fingerprint(a[str(k)]) == str(sha), f"{k}: first entries {got} vs the reference's {head}"
 
 
 def test_cpu_tensors_are_refused_not_silently_computed():

@@ -6,7 +6,7 @@ A=$1; B=$2; shift 2
 for rep in 1 2; do
   for L in $A $B; do
     echo "== $L (rep $rep)"
-    TQDNE_HIP_LIB=$PWD/tqdne_amd/lib/$L python3 bench.py "$@" 2>/dev/null | python3 -c "
+    TQDNE_HIP_LIB=$PWD/tqdne_amd/lib/$L python3 bench.py --full "$@" 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()

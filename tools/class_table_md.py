@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the per-class tables of a bench.py JSON line (kernel_classes) as the markdown used in DESIGN.md section 5."""
+"""Print the per-class tables of a `bench.py --full` JSON line (kernel_classes) as the markdown used in DESIGN.md section 5."""
 import json, sys
 d = json.load(open(sys.argv[1]))
 for sec, t in d["kernel_classes"].items():

@@ -9,7 +9,7 @@ L=$PWD/tqdne_amd/lib
 for rep in 1 2; do
 for v in hip nomma noepi mmaonly nostage; do
   echo "== $v rep $rep" >> $OUT/sample_bounds.txt
-  TQDNE_HIP_LIB=$L/libtqdne_$v.so python3 bench.py --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+  TQDNE_HIP_LIB=$L/libtqdne_$v.so python3 bench.py --full --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()

@@ -20,7 +20,7 @@ for v in hip ncb4 ncb4_norefill nostage now; do
   lib=$L/libtqdne_$v.so; [ $v = hip ] && lib=$L/libtqdne_hip.so
   ncb=0; case $v in ncb4*) ncb=1;; esac
   echo "== $v rep $rep" >> $OUT/sample_gate.txt
-  TQDNE_HIP_LIB=$lib TQDNE_CONV_NCB4=$ncb python3 bench.py --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+  TQDNE_HIP_LIB=$lib TQDNE_CONV_NCB4=$ncb python3 bench.py --full --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()

@@ -6,7 +6,7 @@ L=$PWD/tqdne_amd/lib
 for rep in 1 2; do
 for v in hip sch0_u2 sch0_u1; do
   echo "== $v rep $rep" >> $OUT/sch0_units.txt
-  TQDNE_HIP_LIB=$L/libtqdne_$v.so python3 bench.py --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+  TQDNE_HIP_LIB=$L/libtqdne_$v.so python3 bench.py --full --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()
@@ -17,7 +17,7 @@ for line in sys.stdin:
 done
 done
 cat $OUT/sch0_units.txt
-for rep in 1 2; do python bench.py --mode train --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+for rep in 1 2; do python bench.py --full --mode train --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line=line.strip()

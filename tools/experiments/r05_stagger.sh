@@ -11,7 +11,7 @@ done
 for rep in 1 2; do
 for s in 0 8 16 32; do
   echo "== stagger $s rep $rep" >> $OUT/stagger_sample.txt
-  TQDNE_HIP_LIB=$L TQDNE_CONV_STAGGER=$s python3 bench.py --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+  TQDNE_HIP_LIB=$L TQDNE_CONV_STAGGER=$s python3 bench.py --full --mode sample --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()

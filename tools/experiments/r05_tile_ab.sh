@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 OUT=gpurun_out/r05g; mkdir -p $OUT
 run() {
-  python3 bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
+  python3 bench.py --full "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()

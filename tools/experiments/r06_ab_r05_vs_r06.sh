@@ -19,10 +19,10 @@ for rep in 1 2 3; do
   echo "== tree _r05 rep $rep" >> $OUT/ab.txt
   (cd _r05 && python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null) | python3 -c "$summ" >> $OUT/ab.txt
   echo "== tree . rep $rep" >> $OUT/ab.txt
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs --no-pmc 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs --no-pmc 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
 done
 echo "== tree _r05, other configurations" >> $OUT/ab.txt
 (cd _r05 && python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables 2>/dev/null) | python3 -c "$summ" >> $OUT/ab.txt
 echo "== tree ., other configurations" >> $OUT/ab.txt
-python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-pmc 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-tables --no-pmc 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
 cat $OUT/ab.txt

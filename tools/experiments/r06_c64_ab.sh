@@ -17,7 +17,7 @@ for rep in 1 2 3; do
 for on in 0 1; do
   for mode in sample train step; do
     echo "== c64=$on mode=$mode rep=$rep" >> $OUT/ab.txt
-    TQDNE_CONV_MX6_C64=$on TQDNE_DGRAD_MX6_C64=$on python3 bench.py --mode $mode --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+    TQDNE_CONV_MX6_C64=$on TQDNE_DGRAD_MX6_C64=$on python3 bench.py --full --mode $mode --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
   done
 done
 done

@@ -18,7 +18,7 @@ run() {  # name, env...
   name=$1; shift
   for mode in sample train; do
     echo "== $name mode=$mode rep=$rep" >> $OUT/ab.txt
-    env "$@" python3 bench.py --mode $mode --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+    env "$@" python3 bench.py --full --mode $mode --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
   done
 }
 for rep in 1 2 3; do

@@ -15,9 +15,9 @@ for line in sys.stdin:
 for rep in 1 2 3; do
 for on in 0 1; do
   echo "== fold=$on tiny B=4 rep=$rep" >> $OUT/ab.txt
-  TQDNE_GN_FOLD_SMALL=$on python3 bench.py --config tiny --batch 4 --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+  TQDNE_GN_FOLD_SMALL=$on python3 bench.py --full --config tiny --batch 4 --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
   echo "== fold=$on paper B=4 rep=$rep" >> $OUT/ab.txt
-  TQDNE_GN_FOLD_SMALL=$on python3 bench.py --config paper --batch 4 --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
+  TQDNE_GN_FOLD_SMALL=$on python3 bench.py --full --config paper --batch 4 --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "$summ" >> $OUT/ab.txt
 done
 done
 for on in 0 1; do

@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 OUT=$PWD/gpurun_out/r06i; mkdir -p $OUT
 run() { name=$1; shift
   echo "== $name rep=$rep" >> $OUT/ab.txt
-  env "$@" python3 bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['parts'])" >> $OUT/ab.txt
+  env "$@" python3 bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['parts'])" >> $OUT/ab.txt
 }
 for rep in 1 2 3; do
   run default TQDNE_BWD_HIPRIO=0

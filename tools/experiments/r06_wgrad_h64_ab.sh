@@ -13,7 +13,7 @@ for s in 256 1024; do
 done
 for rep in 1 2 3; do for on in 0 1; do
   echo "== train step, TQDNE_WGRAD_H64=$on rep=$rep" >> $OUT/ab.txt
-  TQDNE_WGRAD_H64=$on python3 bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['parts'])" >> $OUT/ab.txt
+  TQDNE_WGRAD_H64=$on python3 bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-tables --no-other-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['parts'])" >> $OUT/ab.txt
 done; done
 for on in 0 1; do TQDNE_WGRAD_H64=$on python3 tools/layer_table.py 64 4096 5 train > $OUT/layers_train_b64_h64_$on.txt 2>/dev/null; done
 cat $OUT/ab.txt

@@ -11,7 +11,7 @@ for ln in open(f"gpurun_out/r04_u_{l}.json"):
         print(l, "ms/step", round(d["ms_per_step"],2), {k:round(v,2) for k,v in d["parts"].items()}, "after", ex.get("train_ms_exchange_after_backward"), "under", ex.get("train_ms_exchange_under_backward"))
 PY
 }
-A="--steps 5 --warmup 2 --no-cpu-baseline --no-tables --no-other-configs"
+A="--full --steps 5 --warmup 2 --no-cpu-baseline --no-tables --no-other-configs"
 run step_plain X=1 timeout 300 python bench.py $A
 run step_forced_reserve_first TQDNE_BENCH_FORCE_RCCL=1 timeout 300 python bench.py $A
 run step_forced_rccl_first TQDNE_BENCH_FORCE_RCCL=1 TQDNE_BENCH_RESERVE_STREAMS_FIRST=0 timeout 300 python bench.py $A
