@@ -25,7 +25,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define TQ_ABI_VERSION 7
+#define TQ_ABI_VERSION 8
 
 #define TQ_ERR_ARG (-1)   /* null / inconsistent pointer arguments */
 #define TQ_ERR_SHAPE (-2) /* unsupported shape */
@@ -373,6 +373,21 @@ int tq_attention_bwd_ws(const float* qkv, const float* out, const float* dout, c
  * (its first half stays unused).  Gradients bit-identical to tq_attention_bwd_ws. */
 int tq_attention_bwd_ws_kv(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                            void* workspace, const void* kv_planes, int B, int T, int H, int D, hipStream_t stream);
+
+/* ABI 8.  Every head size D with 8 | D and 8 <= D <= 256 (attention_hd.hip): the first-generation kernels on the smallest tile in
+ * {32, 64, 128, 256} that holds the head; channels >= D are zero-filled on load and skipped on store, strides and the D^-1/4 scale are
+ * those of the true D.  Same tensors and layouts as tq_attention_fwd / tq_attention_bwd.  The entry points above keep their contract
+ * (D in {32, 64, 128}, TQ_ERR_SHAPE otherwise).
+ *   tq_attention_head_tile: the tile width for head size D, 0 where there is no kernel (needs no device).
+ *   tq_attention_hd_lds_bytes: dynamic LDS of a launch, pass 0 forward, 1 dQ, 2 dK / dV; 0 without a kernel (needs no device).
+ *   tq_attention_hd_workspace_bytes: the partial rows of the forward's key split; workspace == NULL never splits.
+ *   tq_attention_bwd_hd: `workspace` is reserved (these kernels take no scratch) and may be NULL. */
+int tq_attention_head_tile(int D);
+size_t tq_attention_hd_lds_bytes(int D, int pass);
+size_t tq_attention_hd_workspace_bytes(int B, int T, int H, int D);
+int tq_attention_fwd_hd(const float* qkv, float* out, float* lse, void* workspace, int B, int T, int H, int D, hipStream_t stream);
+int tq_attention_bwd_hd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
+                        void* workspace, int B, int T, int H, int D, hipStream_t stream);
 
 /* ---- EDM / sampler elementwise ------------------------------------------------------------------------------ */
 /* per-sample scalars from sigma: c_in, c_out, c_skip, c_noise, loss weight  (edm.py:24-37); sigma_stride 0 = shared */

@@ -1,0 +1,359 @@
+"""Attention for every head size d with 8 | d, 8 <= d <= 256 (csrc/attention_hd.hip) on the GPU: the kernels against the fp64 formula
+and the reference's own recorded output, equality with the established kernels at 32 / 64 / 128, and whole models that land on head
+sizes 8, 16, 96 and 256 against the CPU oracle.  Bars: forward 1e-4 and log-sum-exp 1e-5 (tests/test_hip_ops.py), dqkv 2e-4
+(tests/test_hip_bwd.py), whole path 1e-3 (tests/test_hip_unet.py)."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, grad_err, rel_err
+
+pytestmark = pytest.mark.gpu
+
+TOL_FWD, TOL_LSE, TOL_BWD, TOL_PATH = 1e-4, 1e-5, 2e-4, 1e-3
+SENTINEL = 12345.0
+CASES = [(4, 16, 70), (3, 8, 64), (2, 48, 130), (1, 96, 200), (2, 136, 127), (1, 256, 150), (2, 256, 512)]   # (H, d, T)
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def cl(x):  # (B,C,T) -> channels-last (B,T,C) on device
+    return x.permute(0, 2, 1).contiguous().to(dev())
+
+
+def ncw(y):  # device (B,T,C) -> cpu (B,C,T)
+    return y.permute(0, 2, 1).cpu()
+
+
+def perturbed_state(model, seed):
+    """zero-init convs re-drawn and GroupNorm affines jittered (same recipe as tools/make_goldens.py)"""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, v in model.state_dict().items():
+        v = v.clone()
+        is_gn = v.ndim == 1 and (".in_layers.0." in k or ".out_layers.0." in k or ".norm." in k or k.startswith("out.0."))
+        if is_gn and k.endswith("weight"):
+            v = 1.0 + 0.1 * torch.randn(v.shape, generator=g)
+        elif is_gn and k.endswith("bias"):
+            v = 0.1 * torch.randn(v.shape, generator=g)
+        elif torch.count_nonzero(v) == 0:
+            v = 0.02 * torch.randn(v.shape, generator=g)
+        sd[k] = v
+    return sd
+
+
+def reference(qkv, H, dout=None):
+    """QKVAttention (blocks.py:156-190) in fp64: output (B, H d, T), log-sum-exp (B, H, T) and, given ``dout``, the qkv gradient"""
+    B, C3, T = qkv.shape
+    D = C3 // (3 * H)
+    x = qkv.double().requires_grad_(dout is not None)
+    q, k, v = x.chunk(3, dim=1)
+    sc = 1 / math.sqrt(math.sqrt(D))
+    w = torch.einsum("bct,bcs->bts", (q * sc).reshape(B * H, D, T), (k * sc).reshape(B * H, D, T))
+    out = torch.einsum("bts,bcs->bct", torch.softmax(w, dim=-1), v.reshape(B * H, D, T)).reshape(B, -1, T)
+    lse = torch.logsumexp(w, dim=-1).reshape(B, H, T)
+    grad = None
+    if dout is not None:
+        out.backward(dout.double())
+        grad = x.grad
+    return out.detach(), lse.detach(), grad
+
+
+def guarded(*shape):
+    """a NaN-filled device tensor of ``shape`` with 4096 sentinel floats in front of and behind it: (tensor, check)"""
+    n, G = math.prod(shape), 4096
+    flat = torch.full((n + 2 * G,), SENTINEL, device=dev())
+    body = flat[G:G + n].view(*shape)
+    body.fill_(float("nan"))
+
+    def check():
+        assert not torch.isnan(body).any(), "a value that should have been written was not"
+        assert bool((flat[:G] == SENTINEL).all()) and bool((flat[G + n:] == SENTINEL).all()), "write outside the buffer"
+    return body, check
+
+
+def run_case(B, H, D, T, seed, peaked=False):
+    from tqdne_amd import ops
+    g = torch.Generator().manual_seed(seed)
+    qkv = torch.randn(B, 3 * H * D, T, generator=g) * (1.0 if peaked else 1.2)
+    if peaked:   # (tests/test_hip_ops.py::test_attention_key_split_for_grids_far_below_the_chip)
+        qkv[:, :2 * H * D] *= 2.5                      # q, k: score standard deviation ~ 6
+        qkv[:, H * D:2 * H * D, T // 3] *= 3.0         # one key far outside the others' range
+    dout = torch.randn(B, H * D, T, generator=g)
+    ref, ref_lse, ref_grad = reference(qkv, H, dout)
+    x, dy = cl(qkv), cl(dout)
+    results = {}
+    for ws in (True, False):
+        out, chk_o = guarded(B, T, H * D)
+        lse, chk_l = guarded(B, H, T)
+        ops.attention(x, H, return_lse=True, workspace=ws, out=out, lse=lse)
+        torch.cuda.synchronize()
+        chk_o(), chk_l()
+        e_o, e_l = rel_err(ncw(out), ref), rel_err(lse.cpu(), ref_lse)
+        dqkv, chk_g = guarded(B, T, 3 * H * D)
+        ops.attention_bwd(x, out, dy, lse, H, workspace=ws, dqkv=dqkv)
+        torch.cuda.synchronize()
+        chk_g()
+        got = ncw(dqkv)
+        e_g = [rel_err(got[:, i * H * D:(i + 1) * H * D], ref_grad[:, i * H * D:(i + 1) * H * D]) for i in range(3)]
+        print(f"B={B} H={H} d={D} T={T} workspace={ws}: out {e_o:.2e} lse {e_l:.2e} dq {e_g[0]:.2e} dk {e_g[1]:.2e} dv {e_g[2]:.2e}")
+        assert e_o < TOL_FWD and e_l < TOL_LSE and max(e_g) < TOL_BWD, (ws, e_o, e_l, e_g)
+        results[ws] = (out.clone(), lse.clone())
+    return results
+
+
+@pytest.mark.parametrize("B", [2, 1])
+@pytest.mark.parametrize("H,D,T", CASES)
+def test_attention_forward_and_backward_vs_fp64(H, D, T, B):
+    run_case(B, H, D, T, seed=H * D + T + B)
+
+
+@pytest.mark.parametrize("B,H,D,T", [(4, 1, 256, 512), (1, 1, 256, 65), (5, 1, 96, 512), (2, 2, 96, 333)])
+def test_key_split_on_peaked_scores(B, H, D, T):
+    """grids far below the chip (B * H * query tiles < 128): with the workspace the key tiles are dealt over several workgroups and a
+    combine launch merges them; the splits' maxima differ by tens here"""
+    assert B * H * ((T + 63) // 64) < 128
+    r = run_case(B, H, D, T, seed=B * 1000 + T, peaked=True)
+    assert rel_err(r[True][0].cpu(), r[False][0].cpu()) < 2e-5 and rel_err(r[True][1].cpu(), r[False][1].cpu()) < TOL_LSE
+
+
+@pytest.mark.parametrize("H,D,T", [(2, 32, 190), (4, 64, 512), (1, 64, 127), (1, 128, 512), (2, 128, 100)])
+def test_new_entry_points_equal_the_established_kernels_bit_for_bit(H, D, T):
+    """at head sizes 32 / 64 / 128 the new kernels run with every mask true: same arithmetic in the same order as the first-generation
+    kernels (``workspace=False``: tq_attention_fwd without planes, tq_attention_bwd)"""
+    from tqdne_amd import ops
+    g = torch.Generator().manual_seed(H * D + T)
+    B = 2
+    x = cl(torch.randn(B, 3 * H * D, T, generator=g) * 1.5)
+    dy = cl(torch.randn(B, H * D, T, generator=g))
+    out0, lse0 = ops.attention(x, H, return_lse=True, workspace=False)
+    out1, lse1 = ops.attention(x, H, return_lse=True, workspace=False, hd=True)
+    assert torch.equal(out0, out1) and torch.equal(lse0, lse1)
+    g0 = ops.attention_bwd(x, out0, dy, lse0, H, workspace=False)
+    g1 = ops.attention_bwd(x, out0, dy, lse0, H, workspace=False, hd=True)
+    assert torch.equal(g0, g1)
+    if D == 128:   # (with a workspace the established path for 128 is the same kernel with its key split: B * H * tiles < 128 here)
+        out2, lse2 = ops.attention(x, H, return_lse=True, workspace=True)
+        out3, lse3 = ops.attention(x, H, return_lse=True, workspace=True, hd=True)
+        assert torch.equal(out2, out3) and torch.equal(lse2, lse3)
+
+
+def test_ops_vs_the_references_recorded_output():
+    """tests/golden/head_size_ops.npz: QKVAttention(H) of the reference and its autograd's qkv gradient, head sizes 16, 48, 96, 256"""
+    from tqdne_amd import ops
+    z = np.load(os.path.join(GOLDEN, "head_size_ops.npz"), allow_pickle=False)
+    assert sorted(int(c[1]) for c in z["cases"]) == [16, 48, 96, 256]
+    for H, D, T in (tuple(int(v) for v in c) for c in z["cases"]):
+        key = f"H{H}:D{D}:T{T}"
+        qkv, dout = (torch.from_numpy(z[f"{key}:{k}"].astype(np.float32)) for k in ("qkv", "dout"))
+        out, lse = ops.attention(cl(qkv), H, return_lse=True)
+        dqkv = ops.attention_bwd(cl(qkv), out, cl(dout), lse, H)
+        e_o, e_g = rel_err(ncw(out), z[key + ":out"]), rel_err(ncw(dqkv), z[key + ":dqkv"])
+        print(f"{key}: out {e_o:.2e} dqkv {e_g:.2e}")
+        assert e_o < TOL_FWD and e_g < TOL_BWD
+
+
+@pytest.mark.parametrize("T", [200, 196])
+def test_micro_unet_head_sizes_8_and_16_vs_the_references_recorded_output(T):
+    from test_head_sizes_host import load_head_size_unet
+    from tqdne_amd import UNetModel
+    sd, d, cfg = load_head_size_unet()
+    m = UNetModel(**cfg)
+    m.load_state_dict(sd)
+    m = m.to(dev()).eval()
+    with torch.no_grad():
+        y = m(*(torch.from_numpy(d[f"T{T}:{k}"]).to(dev()) for k in ("x", "t", "cond"))).cpu()
+    e = rel_err(y, d[f"T{T}:y"])
+    print(f"head-size micro unet T={T}: {e:.2e}")
+    assert e < TOL_PATH
+    eng = m._engine(2, T, dev())
+    assert sum(_name(op[0]) == "tq_attention_fwd_hd" for op in eng.ops) == sum(t[0] == "attn" for t in eng.tape) == 7
+
+
+# ---- whole models ------------------------------------------------------------------------------------------------------------------
+
+def _name(fn):
+    return getattr(fn, "__name__", "")
+
+
+def head_cfg(which):
+    from tqdne_amd import paper_1d_unet_config, tiny_1d_unet_config
+    if which == "paper_h256":     # the paper config with num_heads left at the class default: one head of 256 channels
+        cfg = paper_1d_unet_config()
+        del cfg["num_heads"]
+        return cfg
+    if which == "paper_h16":      # 256 channels over 16 heads
+        return dict(paper_1d_unet_config(), num_heads=16)
+    if which == "wide_h96":       # the config of test_wide_unet_model_channels_128_vs_oracle with 384 channels over 4 heads
+        return dict(tiny_1d_unet_config(), model_channels=128, channel_mult=(1, 2, 3), num_res_blocks=1, num_heads=4)
+    if which == "mid_h96":        # 192 channels over 2 heads in the middle block (widths 64 / 128 / 192)
+        return dict(tiny_1d_unet_config(), model_channels=64, channel_mult=(1, 2, 3), num_res_blocks=1, num_heads=2)
+    if which == "narrow_h96":     # one head of 96 channels in the middle block (widths 32 / 64 / 96)
+        return dict(tiny_1d_unet_config(), model_channels=32, channel_mult=(1, 2, 3), num_res_blocks=1, num_heads=1)
+    raise KeyError(which)
+
+
+def forward_vs_oracle(cfg, B, T, seed=17):
+    from oracle import unet as OU
+    from tqdne_amd import UNetModel
+    torch.manual_seed(0)
+    m = UNetModel(**cfg)
+    sd = perturbed_state(m, seed)
+    m.load_state_dict(sd)
+    m = m.to(dev()).eval()
+    g = torch.Generator().manual_seed(1234)
+    x = torch.randn(B, 3, T, generator=g)
+    t = torch.randn(B, generator=g) * 0.5
+    c = torch.randn(B, 5, generator=g) if cfg.get("cond_features") else None
+    with torch.no_grad():
+        y = m(x.to(dev()), t.to(dev()), c.to(dev()) if c is not None else None).cpu()
+        yo = OU.unet_forward(sd, cfg, x, t, c)
+    eng = m._engine(B, T, dev())
+    assert any(_name(op[0]) == "tq_attention_fwd_hd" for op in eng.ops) and any(_name(op[0]) == "tq_attention_fwd_hd" for op in eng.ops_infer)
+    return rel_err(y, yo)
+
+
+@pytest.mark.parametrize("which,B,T", [("paper_h256", 2, 4096), ("paper_h256", 1, 4064), ("paper_h16", 2, 512), ("wide_h96", 2, 512),
+                                       ("mid_h96", 2, 512), ("narrow_h96", 2, 512)])
+def test_unet_forward_vs_oracle(which, B, T):
+    e = forward_vs_oracle(head_cfg(which), B, T)
+    print(f"{which} unet B={B} T={T}: rel err vs oracle {e:.2e}")
+    assert e < TOL_PATH
+
+
+def test_unet_with_the_class_default_arguments_vs_oracle():
+    """UNetModel(3, 32, 3, 2, dims=1): channel_mult (1, 2, 4, 8), attention at 8x on 256 channels with one head, conv_kernel_size 3"""
+    cfg = dict(in_channels=3, model_channels=32, out_channels=3, num_res_blocks=2, dims=1)
+    e = forward_vs_oracle(cfg, 2, 256)
+    print(f"class-default unet: rel err vs oracle {e:.2e}")
+    assert e < TOL_PATH
+
+
+_ORACLE_GRADS = {}
+
+
+def oracle_grads(which, B, T):
+    """(state dict, batch, oracle loss, oracle gradients) of the EDM loss -- computed once per config (autograd through the CPU oracle at
+    the paper's size takes a while)"""
+    if which not in _ORACLE_GRADS:
+        from oracle import edm as OE
+        from tqdne_amd import LightningEDM
+        cfg = dict(head_cfg(which), dropout=0.0)
+        torch.manual_seed(0)
+        sd = perturbed_state(LightningEDM(cfg, {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0}).unet, 23)
+        g = torch.Generator().manual_seed(77)
+        sig = 0.5 * torch.randn(B, 3, T, generator=g)
+        cond = torch.randn(B, 5, generator=g) if cfg["cond_features"] else None
+        eps, noise = torch.randn(B, generator=g), torch.randn(B, 3, T, generator=g)
+        params = {("unet." + k): v.clone().requires_grad_(k != "time_embed.W") for k, v in sd.items()}
+        lo = OE.loss_step(OE.EDMParams(), OE.make_net(params, cfg), sig, eps, noise, cond=cond)
+        lo.backward()
+        _ORACLE_GRADS[which] = (cfg, sd, (sig, eps, noise, cond), lo.detach(), {k: v.grad for k, v in params.items()})
+    return _ORACLE_GRADS[which]
+
+
+@pytest.mark.parametrize("which,B,T,ckpt", [("paper_h256", 2, 4096, False), ("paper_h256", 2, 4096, True), ("paper_h16", 2, 512, False),
+                                            ("mid_h96", 2, 512, False), ("narrow_h96", 2, 512, False)])
+def test_gradients_vs_oracle(which, B, T, ckpt):
+    """every parameter gradient of the EDM loss vs torch autograd through the CPU oracle; ``ckpt``: the same with use_checkpoint=True,
+    whose backward re-issues the attention forward.
+
+    Head size 96 is held on 192 and 96 channels, not on the 384 of ``wide_h96``: the backward of a 384-channel attention block is
+    refused by a launch that is not attention -- tq_colsum takes at most 1024 channels and the qkv projection's output gradient has
+    3 x 384 = 1152 (``colsum:middle_block.1.qkv`` returns TQ_ERR_SHAPE; the forward of that model passes above).  A limit of the
+    column-sum kernel, independent of the head size and left as it is here."""
+    from tqdne_amd import LightningEDM
+    cfg, sd, (sig, eps, noise, cond), lo, ref = oracle_grads(which, B, T)
+    edm = LightningEDM(dict(cfg, use_checkpoint=ckpt), {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0})
+    edm.unet.load_state_dict(sd)
+    edm = edm.to(dev()).train()
+    loss = edm.step_with_noise(sig.to(dev()), eps.to(dev()), noise.to(dev()), cond=cond.to(dev()) if cond is not None else None)
+    loss.backward()
+    assert rel_err(loss.detach().cpu(), lo) < TOL_PATH
+    eng = edm.unet._engine(B, T, dev())
+    assert eng.ckpt == ckpt
+    assert any(_name(op[0]) == "tq_attention_bwd_hd" for op in eng._bwd.ops)
+    if ckpt:
+        assert any(op[2].startswith("recompute:") and _name(op[0]) == "tq_attention_fwd_hd" for op in eng._bwd.ops)
+    gmax = max(float(v.abs().max()) for v in ref.values() if v is not None)
+    worst, wname = 0.0, ""
+    for name, p in edm.unet.named_parameters():
+        if not p.requires_grad:
+            continue
+        e = grad_err(p.grad, ref["unet." + name], gmax, name)
+        if e > worst:
+            worst, wname = e, name
+    print(f"{which} ckpt={ckpt}: loss {float(loss):.6f}; worst gradient rel err {worst:.2e} at {wname}")
+    assert worst < TOL_PATH
+
+
+def _edm_h256(num_steps):
+    from tqdne_amd import LightningEDM
+    cfg = dict(head_cfg("paper_h256"), dropout=0.0)
+    torch.manual_seed(0)
+    edm = LightningEDM(cfg, {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0}, num_sampling_steps=num_steps)
+    sd = perturbed_state(edm.unet, 41)
+    edm.unet.load_state_dict(sd)
+    return edm.to(dev()).eval(), sd, cfg
+
+
+def test_sampler_18_steps_vs_oracle():
+    from oracle import edm as OE
+    edm, sd, cfg = _edm_h256(18)
+    g = torch.Generator().manual_seed(3)
+    B, T = 4, 512
+    start = torch.randn(B, 3, T, generator=g, dtype=torch.float64)
+    cond = torch.randn(B, 5, generator=g)
+    sig = OE.sampling_sigmas(OE.EDMParams(), 18)
+    out = edm.sample_deterministically((start * sig[0]).to(dev()), sig.to(dev()), None, cond.to(dev()))
+    with torch.no_grad():
+        ref = OE.sample_deterministic(OE.EDMParams(), OE.make_net({("unet." + k): v for k, v in sd.items()}, cfg), start, 18, cond=cond)
+    e = rel_err(out.cpu(), ref)
+    print(f"head size 256, 18-step sample (35 NFE): {e:.2e}")
+    assert e < TOL_PATH
+
+
+def test_two_lane_sampler_is_bit_identical():
+    """half batches on two streams integrate exactly the same per-sample arithmetic: concurrent attention launches of the new kernels
+    (separate streams, one shared library) do not disturb each other"""
+    from oracle import edm as OE
+    import tqdne_amd.engine as E
+    edm, _, _ = _edm_h256(4)
+    sig = OE.sampling_sigmas(OE.EDMParams(), 4).to(dev())
+    g = torch.Generator().manual_seed(31)
+    B = 16
+    start = torch.randn(B, 3, 256, generator=g, dtype=torch.float64).to(dev()) * sig[0]
+    cond = torch.randn(B, 5, generator=g).to(dev())
+    old_w = E.SMALL_TILE_WGS
+    try:
+        E.SMALL_TILE_WGS = 0   # (same tiles in the one-lane plan and in the lanes' plans)
+        one = edm.sample_deterministically(start, sig, None, cond, lanes=1)
+        two = edm.sample_deterministically(start, sig, None, cond, lanes=2)
+    finally:
+        E.SMALL_TILE_WGS = old_w
+    assert torch.isfinite(one).all() and torch.equal(one, two)
+    engines = list(edm.unet._engine_cache.values())
+    assert len(engines) >= 3 and all(any(_name(op[0]) == "tq_attention_fwd_hd" for op in e.ops_infer) for e in engines)
+
+
+def test_plans_of_the_established_head_sizes_do_not_reach_the_new_entry_points():
+    """the paper plan (4 heads of 64) and the tiny plan (one head of 128), forward, inference and backward op lists"""
+    from tqdne_amd import LightningEDM, paper_1d_unet_config, tiny_1d_unet_config
+    for cfg in (paper_1d_unet_config(), tiny_1d_unet_config()):
+        torch.manual_seed(0)
+        edm = LightningEDM(dict(cfg, dropout=0.0), {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0}).to(dev()).train()
+        B, T = 1, 512
+        g = torch.Generator().manual_seed(1)
+        cond = torch.randn(B, 5, generator=g).to(dev()) if cfg["cond_features"] else None
+        loss = edm.step_with_noise(torch.randn(B, 3, T, generator=g).to(dev()), torch.randn(B, generator=g).to(dev()),
+                                   torch.randn(B, 3, T, generator=g).to(dev()), cond=cond)
+        loss.backward()
+        eng = edm.unet._engine(B, T, dev())
+        names = [_name(op[0]) for ops in (eng.ops, eng.ops_infer, eng._bwd.ops) for op in ops]
+        assert sum(t[0] == "attn" for t in eng.tape) >= 1 and "tq_attention_fwd" in names
+        assert not any(n.endswith("_hd") for n in names), [n for n in names if n.endswith("_hd")]

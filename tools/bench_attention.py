@@ -1,10 +1,45 @@
 #!/usr/bin/env python3
 """Time the attention kernels on the paper shape (B=64, T=512, 4 heads x 64) and report their error against an fp64 torch
-evaluation of the reference's QKVAttention (tqdne/blocks.py:156-190).  usage: bench_attention.py [B] [T] [H] [D] [reps]"""
+evaluation of the reference's QKVAttention (tqdne/blocks.py:156-190).  usage: bench_attention.py [B] [T] [H] [D] [reps]
+
+Kernel time of one launch shape, for comparing head sizes (d = 256 x 1 head against 64 x 4; 96 against 128), in two steps:
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_attention.py --launches B T H D ITERS
+      issues ITERS training forwards (with log-sum-exp and workspace, as the engine does) and ITERS backwards of that one shape;
+  python tools/bench_attention.py --sum-stats ITERS OUT
+      adds up, from the *kernel_stats.csv under OUT, the time of every attention kernel (prep, combine and delta launches
+      included) per iteration, forward and backward apart."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+if sys.argv[1:2] == ["--sum-stats"]:
+    import csv, glob
+    iters, root = int(sys.argv[2]), sys.argv[3]
+    tot = {"fwd": 0.0, "bwd": 0.0}
+    for path in glob.glob(os.path.join(root, "**", "*kernel_stats.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            name = row["Name"]
+            if "att" not in name:
+                continue
+            tot["bwd" if ("bwd" in name or "delta" in name) else "fwd"] += float(row["TotalDurationNs"])
+            print(f"  {float(row['TotalDurationNs']) / iters * 1e-3:9.1f} us/iter  {row['Calls']:>5} calls  {name[:110]}")
+    print(f"attention kernels per iteration: fwd {tot['fwd'] / iters * 1e-3:.1f} us  bwd {tot['bwd'] / iters * 1e-3:.1f} us")
+    sys.exit(0)
+
 import torch
 from tqdne_amd import ops
+
+if sys.argv[1:2] == ["--launches"]:
+    B, T, H, D, iters = map(int, sys.argv[2:7])
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    qkv = torch.randn(B, T, 3 * H * D, device=dev) * 1.5
+    dout = torch.randn(B, T, H * D, device=dev)
+    for _ in range(iters):
+        out, lse = ops.attention(qkv, H, return_lse=True)
+        ops.attention_bwd(qkv, out, dout, lse, H)
+    torch.cuda.synchronize()
+    print(f"issued {iters} x (forward, backward) at B={B} T={T} H={H} D={D}")
+    sys.exit(0)
 
 B, T, H, D, reps = (list(map(int, sys.argv[1:])) + [64, 512, 4, 64, 50][len(sys.argv) - 1:])[:5]
 dev = torch.device("cuda:0")

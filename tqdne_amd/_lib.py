@@ -26,7 +26,7 @@ PACK_MODE_T = {TQ_WFMT_BF16X3: 1, TQ_WFMT_F16_MX6: 5}                      # ...
 
 
 DEFAULT_SCHEME = "f16mx6"
-ABI_VERSION = 7   # include/tqdne_hip.h TQ_ABI_VERSION
+ABI_VERSION = 8   # include/tqdne_hip.h TQ_ABI_VERSION
 
 
 def requested_scheme() -> str:
@@ -145,6 +145,11 @@ _PROTOS = {
     "tq_attention_bwd": (I, [VP] * 6 + [I, I, I, I, VP]),
     "tq_attention_bwd_ws": (I, [VP] * 7 + [I, I, I, I, VP]),
     "tq_attention_bwd_ws_kv": (I, [VP] * 8 + [I, I, I, I, VP]),
+    "tq_attention_head_tile": (I, [I]),
+    "tq_attention_hd_lds_bytes": (SZ, [I, I]),
+    "tq_attention_hd_workspace_bytes": (SZ, [I, I, I, I]),
+    "tq_attention_fwd_hd": (I, [VP, VP, VP, VP, I, I, I, I, VP]),
+    "tq_attention_bwd_hd": (I, [VP] * 7 + [I, I, I, I, VP]),
     "tq_edm_scalars": (I, [VP, I, F, VP, VP, VP, VP, VP, I, VP]),
     "tq_cm_scalars": (I, [VP, I, F, F, VP, VP, I, VP]),
     "tq_edm_noise_inject": (I, [VP, VP, VP, F, F, VP, VP, I, I, VP]),

@@ -730,9 +730,13 @@ class UNetEngine:
     def _attention(self, x: Act, ab, name: str) -> Act:
         g = self._gn([x], ab.norm)
         D = ab.channels // ab.num_heads
-        if D not in (32, 64, 128):
-            raise NotImplementedError(f"attention head dim {D} (kernels exist for 32, 64 and 128)")
-        ws = self._attn_workspace(self.lib.tq_attention_workspace_bytes(self.B, x.T, ab.num_heads, D))
+        # head sizes 32 / 64 / 128: the established entry points; every other multiple of 8 up to 256: the padded-tile kernels
+        hd = D not in (32, 64, 128)
+        if hd and not self.lib.tq_attention_head_tile(D):
+            raise NotImplementedError(f"attention head dim {D}: kernels exist for multiples of 8 from 8 to 256 "
+                                      "(larger heads need another kernel structure: their K / V tiles do not fit the LDS)")
+        ws_bytes = self.lib.tq_attention_hd_workspace_bytes if hd else self.lib.tq_attention_workspace_bytes
+        ws = self._attn_workspace(ws_bytes(self.B, x.T, ab.num_heads, D), "_attn_ws_hd" if hd else "_attn_ws")
         # inference forwards: the qkv projection writes K / V as the attention kernel's bf16 hi / lo planes itself (no fp32 K / V,
         # no split pass: -134 MB and one launch per block); forwards a backward may follow keep fp32 qkv for tq_attention_bwd
         split = (ws, ab.num_heads, D) if D in (32, 64) else None
@@ -747,7 +751,8 @@ class UNetEngine:
         else:
             lse = self._empty(self.B, ab.num_heads, x.T)
         flops = 4 * ab.channels * x.T * x.T * self.B
-        op = (self.lib.tq_attention_fwd, (_p(qkv.buf), _p(att.buf), _p(lse), _p(ws), self.B, x.T, ab.num_heads, D), "attention", flops)
+        fwd = self.lib.tq_attention_fwd_hd if hd else self.lib.tq_attention_fwd   # (same arguments; inference and training share it for hd)
+        op = (fwd, (_p(qkv.buf), _p(att.buf), _p(lse), _p(ws), self.B, x.T, ab.num_heads, D), "attention", flops)
         if split is not None and not self.ckpt:   # (see enable_block_kv: once a backward plan exists this launch gets a workspace of its own)
             self._attn_train_ops.append((len(self.ops), len(self.tape), ws.numel()))
         infer_op = None
@@ -767,15 +772,16 @@ class UNetEngine:
         self.tape.append(("attn", entry))
         return out
 
-    def _attn_workspace(self, nbytes: int):
+    def _attn_workspace(self, nbytes: int, slot: str = "_attn_ws"):
         """pre-split K/V scratch, shared by the attention blocks of the plan that have one shape (they run back to back on one
         stream); a block that needs more (a Decoder with attention at several resolutions: T grows along up_blocks) gets a
-        buffer of its own -- launches already emitted keep the pointer they were bound to"""
-        ws = getattr(self, "_attn_ws", None)
+        buffer of its own -- launches already emitted keep the pointer they were bound to.  ``slot``: the padded-tile kernels keep
+        their key-split rows in a buffer of their own, away from the planes whose padding rows must stay zero"""
+        ws = getattr(self, slot, None)
         if ws is None or ws.numel() != nbytes:
             ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)  # padding rows (t >= T) stay zero
             self._keep.append(ws)
-            self._attn_ws = ws
+            setattr(self, slot, ws)
         return ws
 
     # ------------------------------------------------------------------ measurement

@@ -486,8 +486,8 @@ class BackwardPlan:
                     return lib.tq_attention_bwd_ws_kv(qkv_p, att_p, datt_p, lse_p, delta_p, dqkv_p, ws_p, kv.data_ptr(), B_, T_, H_, D_, stream)
                 return lib.tq_attention_bwd_ws(qkv_p, att_p, datt_p, lse_p, delta_p, dqkv_p, ws_p, B_, T_, H_, D_, stream)
             fn = attn_bwd
-        else:
-            fn = self.lib.tq_attention_bwd_ws
+        else:   # (head sizes other than 32 / 64 / 128: the padded-tile kernels, which take no scratch either)
+            fn = self.lib.tq_attention_bwd_ws if t["D"] in (32, 64, 128) else self.lib.tq_attention_bwd_hd
         self.ops.append([fn, [_p(qkv.buf), _p(att.buf), _p(datt), _p(t["lse"]), _p(delta), _p(dqkv), _p(ws),
                               B, T, ab.num_heads, t["D"]], "attention bwd"])
         self._wrote(dqkv)

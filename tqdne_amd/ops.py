@@ -127,23 +127,41 @@ def head_conv(x, weight, bias, gscale=None, gshift=None, c_out=None, c_skip=None
     return y
 
 
-def attention(qkv, heads, return_lse=False, workspace=True):
+def _head_dim_route(lib, D, hd):
+    """True: the every-head-size entry points (tq_attention_*_hd); False: the established ones (head sizes 32 / 64 / 128, and every size
+    without a kernel, which they refuse with TQ_ERR_SHAPE)"""
+    return bool(lib.tq_attention_head_tile(D)) and (hd or D not in (32, 64, 128))
+
+
+def attention(qkv, heads, return_lse=False, workspace=True, hd=False, out=None, lse=None):
+    """``hd=True`` forces the every-head-size entry point (the default routes head sizes 32 / 64 / 128 to the established kernels, every
+    other size with a kernel to it); ``out`` / ``lse``: caller-owned result buffers."""
     lib = _lib.load()
     B, T, C3 = qkv.shape
     D = C3 // (3 * heads)
-    out = torch.empty(B, T, heads * D, device=qkv.device)
-    lse = torch.empty(B, heads, T, device=qkv.device) if return_lse else None
+    out = torch.empty(B, T, heads * D, device=qkv.device) if out is None else out
+    if return_lse and lse is None:
+        lse = torch.empty(B, heads, T, device=qkv.device)
+    if _head_dim_route(lib, D, hd):
+        ws = torch.empty(lib.tq_attention_hd_workspace_bytes(B, T, heads, D), dtype=torch.uint8, device=qkv.device) if workspace else None
+        check(lib.tq_attention_fwd_hd(_p(qkv), _p(out), _p(lse), _p(ws), B, T, heads, D, _stream(qkv.device)), "attention (hd)")
+        return (out, lse) if return_lse else out
     ws = torch.empty(lib.tq_attention_workspace_bytes(B, T, heads, D), dtype=torch.uint8, device=qkv.device) if workspace else None
     check(lib.tq_attention_fwd(_p(qkv), _p(out), _p(lse), _p(ws), B, T, heads, D, _stream(qkv.device)), "attention")
     return (out, lse) if return_lse else out
 
 
-def attention_bwd(qkv, out, dout, lse, heads, workspace=True):
+def attention_bwd(qkv, out, dout, lse, heads, workspace=True, hd=False, dqkv=None):
+    """``hd`` as in ``attention``; ``dqkv``: caller-owned result buffer."""
     lib = _lib.load()
     B, T, C3 = qkv.shape
     D = C3 // (3 * heads)
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
     delta = torch.empty(B, heads, T, device=qkv.device)
+    if _head_dim_route(lib, D, hd):
+        check(lib.tq_attention_bwd_hd(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), None, B, T, heads, D,
+                                      _stream(qkv.device)), "attention bwd (hd)")
+        return dqkv
     # (the second-generation kernels exist for D = 32 / 64; D = 128 falls through to the first generation, which takes no scratch)
     ws = (torch.empty(2 * lib.tq_attention_workspace_bytes(B, T, heads, D), dtype=torch.uint8, device=qkv.device)
           if (workspace and D in (32, 64)) else None)
