@@ -49,6 +49,11 @@ typedef struct ihipStream_t* hipStream_t;
  * C_out / 256 times the workgroups (a 16-sample plan alone on the device at T = 512: 64 -> 192; 37 -> 21 us).  Same numbers.  With the
  * device full (B = 64, or four 16-sample lanes) the input-stationary form is the faster one (+0.7 % of a sample with this flag). */
 #define TQ_CONV_CH_TILES 128
+/* TQ_CONV_WIDE_TABLE: take the wide-table instantiation of the fp16 + MX-fp6 forward tiles (the one built for more than 1024
+ * concatenated input channels, see tq_conv1d_max_cin) for a launch of at most 1024 as well.  Same numbers, bit for bit: a switch for
+ * tests and A/B timing.  Launches that are not in TQ_WFMT_F16_MX6 with a TQ_CONV_GN prologue ignore it; TQ_ERR_SHAPE where no wide tile
+ * is built (128 does not divide C_out, TqConvDesc.gn_fold set). */
+#define TQ_CONV_WIDE_TABLE 256
 
 /* TqConvDesc.wfmt: how the fp32 product x * w is contracted on the matrix cores (= format of the packed weights).
  * BF16X3: both operands split into bf16 hi + lo, three bf16 MFMA products; fp32 range, ~2^-16 relative (pack modes 0 / 1).
@@ -174,6 +179,24 @@ int tq_build_flags(void);
 size_t tq_conv_weight_pack_bytes(int C_out, int C_in, int K, int mode);
 int tq_pack_conv_weight(const float* w, int C_out, int C_in, int K, int mode, void* packed, hipStream_t stream);
 int tq_conv_tile_co(int C_out);
+/* Width limits, asked of the library (no device needed; hosts plan with these instead of repeating constants).
+ *   tq_conv1d_max_cin(wfmt, C_out): the most concatenated input channels C_in0 + C_in1 a stride-1 forward launch with a TQ_CONV_GN
+ *     prologue takes in that scheme on the tile chosen for C_out (C_out = 0: on its widest tile); 0 where the scheme has no tile.  TQ_WFMT_F16_MX6 keeps the folded GroupNorm coefficients of a sample in an LDS table:
+ *     1024 entries in the established tiles, 2048 in the wide-table tiles (the 256- and 128-channel tiles of 128 positions and the small
+ *     tile, k in {1, 3, 5}; chosen by the library when C_in0 + C_in1 > 1024).  TQ_WFMT_BF16X3 reads them from global memory: no table, the
+ *     value is the widest shape the suite covers.  TQ_WFMT_F16_MX8 has the 1024-entry table only.  Launches WITHOUT a prologue (fused skip
+ *     sources, resampling convs, data gradients incl. TqConvBwdDesc.C_dy) read no table and have no such limit.
+ *   tq_conv1d_gn_fold_max_cin(wfmt, t_tile, C_out): the most channels for which a launch of that tile accepts TqConvDesc.gn_fold
+ *     (the fold's scratch must fit the tile's staging buffers, and the wide-table tiles do not fold); 0 = this tile never folds.
+ *   tq_conv1d_max_cout(): the most output channels a plan may give a conv (3072: the qkv projection of a 1024-channel attention block,
+ *     the widest shape the suite covers; the kernels themselves tile C_out).
+ *   tq_colsum_max_channels(): the most channels of tq_colsum / tq_gn_bwd_apply_colsum (chunks of <= 1024 channels over the grid). */
+int tq_conv1d_max_cin(int wfmt, int C_out);
+int tq_conv1d_max_cout(void);
+size_t tq_conv1d_wide_lds_bytes(int ktaps, int t_tile, int C_out); /* dynamic LDS of the wide-table tile of a launch; 0 = no such tile */
+int tq_conv1d_gn_table_entries(int wide); /* entries of the coefficient table: 0 the established tiles (1024), 1 the wide-table tiles (2048) */
+int tq_conv1d_gn_fold_max_cin(int wfmt, int t_tile, int C_out);
+int tq_colsum_max_channels(void);
 /* All (re)packs of a plan in one launch (what a training step re-does after every optimizer update: torch parameters ->
  * forward / transposed fragments, plus the gather of the ResBlocks' embedding projections into their concatenated buffers,
  * unet.py:91-97).  jobs: a DEVICE array, block_begin = running sum of tq_pack_job_blocks over the preceding jobs.
@@ -277,7 +300,9 @@ int tq_gn_bwd_apply_colsum(const float* g, const float* x, const float* r, const
                            float* colsum_bc, int bc_stride, float* colsum_c, float* colsum_c2, uint32_t* amax_out,
                            hipStream_t stream);
 /* out_bc[b*bc_stride + c] += bscale[b] * sum_t dy[b,t,c];  out_c[c], out_c2[c] += sum_{b,t} (...)  (each optional; bias and
- * embedding gradients: two biases fed by the same tensor are served by one pass) */
+ * embedding gradients: two biases fed by the same tensor are served by one pass).  4 | C <= tq_colsum_max_channels(): up to 1024
+ * channels are one column per thread; wider tensors (the output gradient of a qkv projection, 3 C) are dealt over the grid in
+ * near-equal chunks of <= 1024 channels, each formed exactly as a launch on that column slice would form it. */
 /* Small fp32 GEMMs of the embedding-MLP backward (unet.py:91-97,210-227,383-388; the autograd of blocks.py:15-26): one launch runs
  * a list of independent products  C (M x N) = A (M x K) * f(B) (K x N) [* silu'(U)]  with strided operands
  * A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn] (a stride of 1 marks the contiguous direction), f = SiLU when pre_b,

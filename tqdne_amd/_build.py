@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libtqdne_hip.so")
-# (the conv kernel template, csrc/conv1d_kernel.hpp, is instantiated by five translation units so that the build runs in parallel)
+# (the conv kernel template, csrc/conv1d_kernel.hpp, is instantiated by seven translation units so that the build runs in parallel)
 SOURCES = ["conv1d_fwd_k5a.hip", "conv1d_fwd_k5b.hip", "conv1d_fwd_k13.hip", "conv1d_resample.hip", "conv1d_dgrad.hip", "conv1d_mfma.hip",
-           "small_ops.hip", "attention.hip", "attention_hd.hip", "backward.hip"]
+           "conv1d_fwd_wide.hip", "conv1d_fwd_wide_k13.hip", "small_ops.hip", "attention.hip", "attention_hd.hip", "backward.hip"]
 # Opt-in kernels that lost their A/B against the default ones: the one-wave-per-SIMD conv (conv1d_w4.hip), the
 # slim 64-channel tile and the in-launch GroupNorm fold (TqGnFuse) inside conv1d_mfma.hip.  TQDNE_BUILD_EXPERIMENTS=1 compiles them
 # (-DTQ_BUILD_EXPERIMENTS) into a library of its own, libtqdne_hip_exp.so, which `_lib` then loads; the default library does not

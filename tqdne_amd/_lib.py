@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
 
 from . import _build
 
@@ -19,6 +20,7 @@ SZ = C.c_size_t
 TQ_CONV_GN, TQ_CONV_SILU, TQ_CONV_EMB, TQ_CONV_RES, TQ_CONV_STATS, TQ_CONV_DROPOUT = 1, 2, 4, 8, 16, 32
 TQ_CONV_POLY2 = 64
 TQ_CONV_CH_TILES = 128
+TQ_CONV_WIDE_TABLE = 256
 TQ_WFMT_BF16X3, TQ_WFMT_F16_MX8, TQ_WFMT_F16_MX6 = 0, 1, 2
 TQ_KV_V_BF16, TQ_KV_V_F16 = 0, 1     # v_format of tq_conv1d_fwd_qkv / tq_attention_fwd_presplit
 PACK_MODE = {TQ_WFMT_BF16X3: 0, TQ_WFMT_F16_MX8: 2, TQ_WFMT_F16_MX6: 3}   # tq_pack_conv_weight mode of a forward weight format
@@ -52,7 +54,19 @@ def attn_v_format() -> int:
 MX6_C64 = os.environ.get("TQDNE_CONV_MX6_C64", "0") == "1"
 
 
-def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, fused_skip: bool = False, k5_act: bool = False) -> int:
+# Sites with more than 1024 concatenated input channels under a GroupNorm prologue (the output blocks of models wider than the paper's): the
+# wide-table fp16 + MX-fp6 tiles (default), or TQDNE_WIDE_MX6=0: bf16x3 for those sites only.
+WIDE_MX6 = os.environ.get("TQDNE_WIDE_MX6", "1") != "0"
+
+
+def conv_max_cin(wfmt: int, C_out: int = 0) -> int:
+    """Most concatenated input channels of a forward conv with a GroupNorm prologue in scheme ``wfmt`` (tq_conv1d_max_cin: asked of the
+    library, needs no device)."""
+    return load().tq_conv1d_max_cin(wfmt, C_out)
+
+
+def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, fused_skip: bool = False, k5_act: bool = False,
+                 gn: Optional[bool] = None) -> int:
     """Contraction scheme of a forward conv launch (include/tqdne_hip.h, TQ_WFMT_*): fp16 + block-scaled corrections where the kernel
     is built for the shape (stride 1 incl. the nearest-upsampling convs, 128 | C_out, 64 | every source's channels incl. a fused skip
     conv's; round 6: also 64 | C_out for the ResBlock convs -- ``k5_act``: k = 5, GN + SiLU prologue, f16mx6 only), bf16x3 elsewhere.
@@ -65,7 +79,15 @@ def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, f
         ok = ok and os.environ.get("TQDNE_FUSED_SKIP_MX8", "1") != "0"
     if not ok or v == "bf16x3":
         return TQ_WFMT_BF16X3
-    return TQ_WFMT_F16_MX6 if v == "f16mx6" else TQ_WFMT_F16_MX8
+    fmt = TQ_WFMT_F16_MX6 if v == "f16mx6" else TQ_WFMT_F16_MX8
+    # width of the site (per-site rule): the fp16-range tiles keep a sample's folded GroupNorm coefficients in an LDS table -- a site
+    # wider than the table of its tile goes to bf16x3, that site only.  ``gn``: the launch has a GroupNorm prologue (assumed when the
+    # caller does not say); launches without one read no table.
+    cin = sum(c for c in list(sources)[:2] if c)
+    if gn is None or gn:
+        if cin > conv_max_cin(fmt, C_out) or (cin > load().tq_conv1d_gn_table_entries(0) and not WIDE_MX6):
+            return TQ_WFMT_BF16X3
+    return fmt
 TQ_BWD_GN, TQ_BWD_SILU, TQ_BWD_DROPOUT, TQ_BWD_ACCUM, TQ_BWD_STATS = 1, 2, 4, 8, 16
 STAT_SLOT = 128
 TQ_AMAX_WAYS, TQ_AMAX_STRIDE = 16, 32           # include/tqdne_hip.h: max|dy| blocks of the column-sum kernels
@@ -130,6 +152,12 @@ _PROTOS = {
     "tq_conv_weight_pack_bytes": (SZ, [I, I, I, I]),
     "tq_pack_conv_weight": (I, [VP, I, I, I, I, VP, VP]),
     "tq_conv_tile_co": (I, [I]),
+    "tq_conv1d_max_cin": (I, [I, I]),
+    "tq_conv1d_max_cout": (I, []),
+    "tq_conv1d_gn_table_entries": (I, [I]),
+    "tq_conv1d_wide_lds_bytes": (SZ, [I, I, I]),
+    "tq_conv1d_gn_fold_max_cin": (I, [I, I, I]),
+    "tq_colsum_max_channels": (I, []),
     "tq_conv1d_fwd": (I, [C.POINTER(TqConvDesc)] + [VP] * 11),
     "tq_conv1d_fwd_skip": (I, [C.POINTER(TqConvDesc)] + [VP] * 13),
     "tq_stem_conv_fwd": (I, [VP] * 6 + [I] * 5 + [VP]),

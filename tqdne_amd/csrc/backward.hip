@@ -955,6 +955,99 @@ __global__ __launch_bounds__(NT) void gn_bwd_apply_cs_kernel(const float* __rest
     colsum_finish<NT>(red, a, mx, active, c4n, nrow, c4, tr, Cs, b, 1.0f, out_bc, bc_stride, out_c, out_c2, amax_out);
 }
 
+// ---- more than 1024 channels (the output gradient of a wide qkv projection: 3 C).  colsum_kernel / gn_bwd_apply_cs_kernel give one
+// float4 column to a thread, i.e. they take C <= 4 NT' with NT' = 256.  These forms deal CHUNKS of at most 1024 channels over
+// gridDim.y: workgroup (x, y) is what colsum_kernel would be on the column slice [y cw, min(C, (y + 1) cw)) of the same rows -- the row
+// stride is the full C, everything else (tiling, order of the additions inside a chunk, one amax word per workgroup) is the same, so
+// each output element is formed exactly as a launch on that slice alone would form it.  C <= 1024 never comes here.
+struct CsChunk { int c0, cw; };   // first channel and width of the workgroup's chunk
+__device__ __forceinline__ CsChunk cs_chunk(int C, int cw) {
+    const int c0 = (int)blockIdx.y * cw;
+    return CsChunk{c0, min(cw, C - c0)};
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void colsum_chunk_kernel(const float* __restrict__ dy, int T, int C, int cw, float* __restrict__ out_bc,
+                                                           int bc_stride, float* __restrict__ out_c, float* __restrict__ out_c2,
+                                                           const float* __restrict__ bscale, unsigned* __restrict__ amax_out, int rpw) {
+    extern __shared__ float red[];
+    const CsChunk ck = cs_chunk(C, cw);
+    const int nsl = (T + rpw - 1) / rpw;
+    const int slot = blockIdx.x % nsl, b = blockIdx.x / nsl;
+    const int c4n = ck.cw >> 2;
+    const int nrow = NT / c4n > 0 ? NT / c4n : 1;
+    const int c4 = threadIdx.x % c4n, tr = threadIdx.x / c4n;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    float mx = 0.f;
+    const bool active = tr < nrow && threadIdx.x < nrow * c4n;
+    if (active) {
+        const int nvalid = min(rpw, T - slot * rpw);
+        const float* src = dy + ((size_t)b * T + (size_t)slot * rpw) * C + ck.c0 + 4 * c4;
+        int tl = tr;
+        for (; tl + 7 * nrow < nvalid; tl += 8 * nrow) {
+            float4 v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4*>(src + (size_t)(tl + q * nrow) * C);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { a.x += v[q].x; a.y += v[q].y; a.z += v[q].z; a.w += v[q].w; }
+            if (amax_out) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) mx = amax4(mx, v[q]);
+            }
+        }
+        for (; tl < nvalid; tl += nrow) {
+            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)tl * C);
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            if (amax_out) mx = amax4(mx, v);
+        }
+    }
+    colsum_finish<NT>(red, a, mx, active, c4n, nrow, c4, tr, ck.cw, b, bscale ? bscale[b] : 1.0f, out_bc ? out_bc + ck.c0 : nullptr, bc_stride,
+                      out_c ? out_c + ck.c0 : nullptr, out_c2 ? out_c2 + ck.c0 : nullptr, amax_out);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void gn_bwd_apply_cs_chunk_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                                    const float* __restrict__ r, const float* __restrict__ cA,
+                                                                    const float* __restrict__ cB, const float* __restrict__ cC,
+                                                                    float* __restrict__ dx, int T, int Cs, int cw, int Ctot, int coff, int accum,
+                                                                    float* __restrict__ out_bc, int bc_stride, float* __restrict__ out_c,
+                                                                    float* __restrict__ out_c2, unsigned* __restrict__ amax_out, int rpw) {
+    extern __shared__ float red[];
+    const CsChunk ck = cs_chunk(Cs, cw);
+    const int nsl = (T + rpw - 1) / rpw;
+    const int slot = blockIdx.x % nsl, b = blockIdx.x / nsl;
+    const int c4n = ck.cw >> 2;
+    const int nrow = NT / c4n > 0 ? NT / c4n : 1;
+    const int c4 = threadIdx.x % c4n, tr = threadIdx.x / c4n;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    float mx = 0.f;
+    const bool active = tr < nrow && threadIdx.x < nrow * c4n;
+    if (active) {
+        const int nvalid = min(rpw, T - slot * rpw);
+        const size_t ko = (size_t)b * Ctot + coff + ck.c0 + 4 * c4;
+        const float4 ka = *reinterpret_cast<const float4*>(cA + ko);
+        const float4 kb = *reinterpret_cast<const float4*>(cB + ko);
+        const float4 kc = *reinterpret_cast<const float4*>(cC + ko);
+        const size_t base = ((size_t)b * T + (size_t)slot * rpw) * Cs + ck.c0 + 4 * c4;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int tl = tr; tl < nvalid; tl += nrow) {   // (same per-element arithmetic as gn_bwd_apply_cs_kernel)
+            const size_t o = base + (size_t)tl * Cs;
+            const float4 gv = *reinterpret_cast<const float4*>(g + o), xv = *reinterpret_cast<const float4*>(x + o);
+            const float4 rv = r ? *reinterpret_cast<const float4*>(r + o) : z4, ov = accum ? *reinterpret_cast<const float4*>(dx + o) : z4;
+            float4 o4 = make_float4(ka.x * gv.x + kb.x * xv.x + kc.x, ka.y * gv.y + kb.y * xv.y + kc.y,
+                                    ka.z * gv.z + kb.z * xv.z + kc.z, ka.w * gv.w + kb.w * xv.w + kc.w);
+            o4.x += rv.x; o4.y += rv.y; o4.z += rv.z; o4.w += rv.w;
+            o4.x += ov.x; o4.y += ov.y; o4.z += ov.z; o4.w += ov.w;
+            *reinterpret_cast<float4*>(dx + o) = o4;
+            a.x += o4.x; a.y += o4.y; a.z += o4.z; a.w += o4.w;
+            mx = amax4(mx, o4);
+        }
+    }
+    colsum_finish<NT>(red, a, mx, active, c4n, nrow, c4, tr, ck.cw, b, 1.0f, out_bc ? out_bc + ck.c0 : nullptr, bc_stride,
+                      out_c ? out_c + ck.c0 : nullptr, out_c2 ? out_c2 + ck.c0 : nullptr, amax_out);
+}
+
+
 __global__ void zero_stuff_kernel(const float* __restrict__ dy, float* __restrict__ out, int T_out, int T_in, int C, size_t n4) {
     const int c4n = C >> 2;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -1039,12 +1132,34 @@ static CsTiling colsum_tiling(int B, int T) {
     return t;
 }
 
+// Channels per chunk of the column-sum kernels: one float4 column per thread of the 256-thread form.  Wider tensors are dealt in
+// near-equal chunks of a multiple of 4 channels over gridDim.y (colsum_chunk_kernel); the limit is the grid's, not a table's.
+constexpr int CS_CHUNK = 1024;
+constexpr int CS_MAX_C = CS_CHUNK * 64;
+static int colsum_chunk_width(int C, int& nchunks) {
+    const int c4 = C / 4;
+    nchunks = (c4 + CS_CHUNK / 4 - 1) / (CS_CHUNK / 4);
+    return ((c4 + nchunks - 1) / nchunks) * 4;
+}
+extern "C" int tq_colsum_max_channels(void) { return CS_MAX_C; }
+
 extern "C" int tq_colsum(const float* dy, int B, int T, int C, float* out_bc, int bc_stride, float* out_c, float* out_c2,
                          const float* bscale, uint32_t* amax_out, hipStream_t stream) {
     if (!dy || (!out_bc && !out_c && !out_c2 && !amax_out)) return TQ_ERR_ARG;
-    if (B <= 0 || T <= 0 || C < 4 || C % 4 || C > 1024) return TQ_ERR_SHAPE;
+    if (B <= 0 || T <= 0 || C < 4 || C % 4 || C > CS_MAX_C) return TQ_ERR_SHAPE;
     const CsTiling tl = colsum_tiling(B, T);
     const int nsl = (T + tl.rows - 1) / tl.rows;
+    if (C > CS_CHUNK) {
+        int nch;
+        const int cw = colsum_chunk_width(C, nch);
+        const size_t shw = (size_t)(tl.nt > cw / 4 ? tl.nt : cw / 4) * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
+        if (tl.nt == 1024)
+            hipLaunchKernelGGL(colsum_chunk_kernel<1024>, dim3(B * nsl, nch), dim3(1024), shw, stream, dy, T, C, cw, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
+        else
+            hipLaunchKernelGGL(colsum_chunk_kernel<256>, dim3(B * nsl, nch), dim3(256), shw, stream, dy, T, C, cw, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
+        TQ_CHECK_LAUNCH();
+        return 0;
+    }
     const int c4n = C / 4;
     const int nrow = tl.nt / c4n > 0 ? tl.nt / c4n : 1;
     const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
@@ -1062,11 +1177,24 @@ extern "C" int tq_gn_bwd_apply_colsum(const float* g, const float* x, const floa
                                       hipStream_t stream) {
     if (!g || !x || !coef_a || !coef_b || !coef_c || !dx) return TQ_ERR_ARG;
     if (colsum_c2 && !colsum_c) return TQ_ERR_ARG;
-    if (B <= 0 || T <= 0 || C_src <= 0 || C_src % 4 || C_src > 1024 || c_offset % 4 || c_offset + C_src > C_total) return TQ_ERR_SHAPE;
+    if (B <= 0 || T <= 0 || C_src <= 0 || C_src % 4 || C_src > CS_MAX_C || c_offset % 4 || c_offset + C_src > C_total) return TQ_ERR_SHAPE;
     if (!colsum_bc && !colsum_c && !amax_out)
         return tq_gn_bwd_apply(g, x, r, coef_a, coef_b, coef_c, dx, B, T, C_src, C_total, c_offset, accumulate, stream);
     const CsTiling tl = colsum_tiling(B, T);
     const int nsl = (T + tl.rows - 1) / tl.rows;
+    if (C_src > CS_CHUNK) {
+        int nch;
+        const int cw = colsum_chunk_width(C_src, nch);
+        const size_t shw = (size_t)(tl.nt > cw / 4 ? tl.nt : cw / 4) * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
+        if (tl.nt == 1024)
+            hipLaunchKernelGGL(gn_bwd_apply_cs_chunk_kernel<1024>, dim3(B * nsl, nch), dim3(1024), shw, stream, g, x, r, coef_a, coef_b, coef_c, dx, T,
+                               C_src, cw, C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
+        else
+            hipLaunchKernelGGL(gn_bwd_apply_cs_chunk_kernel<256>, dim3(B * nsl, nch), dim3(256), shw, stream, g, x, r, coef_a, coef_b, coef_c, dx, T,
+                               C_src, cw, C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
+        TQ_CHECK_LAUNCH();
+        return 0;
+    }
     const int c4n = C_src / 4;
     const int nrow = tl.nt / c4n > 0 ? tl.nt / c4n : 1;
     const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);

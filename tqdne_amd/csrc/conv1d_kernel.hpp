@@ -125,8 +125,13 @@ struct Cfg {
 // is staged ONCE into its own LDS buffers with every load in flight together, then the workgroup runs over all output-channel
 // tiles: no per-chunk barrier / load round trip (a 1x1 chunk has 1/5 of the MFMA work to hide one under) and no re-staging of
 // the same rows by 3 channel-tile workgroups (qkv).
-template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, bool FUSE, int SCH, bool PW = false, int TBW = 8, int NCB = 2>
+// GTW: entries per array of the LDS table of folded GroupNorm coefficients (scheme 2 with a prologue) = the widest concatenated input the
+// instantiation takes.  1024 (one float4 of either array per thread of a 256-thread workgroup) is every established kernel; 2048 (two) is
+// instantiated for the forward tiles in conv1d_fwd_wide*.hip and reached only when C_in > 1024 (dispatch_tile).
+template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, bool FUSE, int SCH, bool PW = false, int TBW = 8, int NCB = 2, int GTW = 1024>
 __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ? 3 : 2)) void conv1d_mfma_kernel(const ConvArgs p) {
+    static_assert(GTW == 1024 || (GTW == 2048 && SCH == 2 && ACT >= 1 && EPI == 0 && !PW && STRIDE == 1 && UPS == 0 && WN == 1 && NCB == 2 && (TBW == 8 || TBW == 2)),
+                  "wide coefficient table: the fp16 + MX-fp6 forward tiles of 128 and 32 positions");
     static_assert(SCH == 0 || STRIDE == 1, "the fp16-range schemes serve stride-1 launches");
     static_assert(EPI != 1 || SCH == 0 || (SCH == 2 && ACT == 0 && !FUSE && !PW), "data gradients: bf16x3, or fp16 + MX-fp6 on a dy scaled into the fp16 range");
     // NCB == 4 (round 4): 256 channels x 128 positions as 4 x 2 waves of 64 channels x 64 positions -- every activation fragment read
@@ -794,12 +799,13 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // Folded GroupNorm coefficients of sample b -> LDS table (read by write16): C_in <= 1024 floats each, i.e. at most ONE float4 of
-    // either array per thread (scheme-2 tiles have >= 256 threads).  Round 5: the two loads are issued HERE and stored to LDS only after
+    // Folded GroupNorm coefficients of sample b -> LDS table (read by write16): C_in <= GTW floats each, i.e. at most GT_N = GTW / 1024
+    // float4 of either array per thread (scheme-2 tiles have >= 256 threads; ONE for every tile but the wide-table ones).  Round 5: the two loads are issued HERE and stored to LDS only after
     // the first chunk's staging loads and the first weight fragments have been requested (gtab_store below), so that the prologue
     // pays one global round trip, not two in a row (table, barrier, then the chunk).  Branch-free: threads past the table repeat
     // its last entry (same value to the same slot).
     static_assert(!(SCH == 2 && ACT >= 1) || C::NTHR >= 256, "one table entry per thread");
+    constexpr int GT_N = GTW / 1024;
     // Round 6, consumer-side GroupNorm fold (TqConvDesc.gn_fold; small tile only): the workgroup forms the folded coefficients of ITS sample
     // from the source tensors' partial statistics here -- the arithmetic of tq_gn_finalize (gn_fold_sample: bit-identical coefficients for
     // any workgroup size) -- writes them where the prologue below (and, later, the backward) reads them, and goes on; every workgroup of
@@ -834,6 +840,17 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
             gt_s = reinterpret_cast<const float4*>(p.gshift + (size_t)b * Cin)[gt_i];
         }
     }
+    // wide table (GT_N == 2): the second entry of a thread, NTHR further on (a 512-thread tile covers 2048 entries with the first alone:
+    // its second entries all repeat the last one)
+    float4 gt_a2 = make_float4(0.f, 0.f, 0.f, 0.f), gt_s2 = gt_a2;
+    int gt_i2 = 0;
+    if constexpr (SCH == 2 && ACT >= 1 && GT_N == 2) {
+        static_assert(GT_N == 1 || 2 * C::NTHR * 4 >= GTW, "two table entries per thread cover the wide table");
+        const int n4 = Cin >> 2;
+        gt_i2 = tid + C::NTHR < n4 ? tid + C::NTHR : n4 - 1;
+        gt_a2 = reinterpret_cast<const float4*>(p.gscale + (size_t)b * Cin)[gt_i2];
+        gt_s2 = reinterpret_cast<const float4*>(p.gshift + (size_t)b * Cin)[gt_i2];
+    }
     auto gtab_store = [&]() __attribute__((always_inline)) {
         if constexpr (SCH == 2 && ACT >= 1) {
             if constexpr (FOLD_LATE) {
@@ -848,6 +865,10 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
             float4* g4 = reinterpret_cast<float4*>(gtab);
             g4[gt_i] = gt_a;
             g4[(Cin >> 2) + gt_i] = gt_s;
+            if constexpr (GT_N == 2) {
+                g4[gt_i2] = gt_a2;
+                g4[(Cin >> 2) + gt_i2] = gt_s2;
+            }
             __syncthreads();
         }
     };
@@ -1440,15 +1461,32 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
 #endif
 }
 
-template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, bool FUSE, int SCH = 0, bool PW = false, int TBW = 8, int NCB = 2>
+// LDS of one workgroup of an instantiation (host-side constant; tq_conv1d_gn_fold_max_cin reads it too)
+template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, int SCH, bool PW, int TBW, int NCB, int GTW>
+struct ConvLds {
+    using C = Cfg<KT, STRIDE, UPS, WM, WN, SCH, TBW, NCB>;
+    // scheme 2 keeps the folded GroupNorm coefficients of the workgroup's sample behind the staging buffers (2 x C_in floats)
+    static constexpr int GTAB_MAX = ((SCH == 2 && ACT >= 1) || (SCH == 0 && TBW == 2 && ACT >= 1 && !PW && EPI == 0)) ? 2 * 4 * GTW : 0;   // room for C_in <= GTW
+    static constexpr int STAGE = PW ? 4 * C::BUF : C::LDS_BYTES;
+    static constexpr int BYTES = STAGE + GTAB_MAX;
+    // the consumer-side GroupNorm fold (TqConvDesc.gn_fold) is built into the established tiles (table of 1024 entries); its scratch
+    // (2 C + 64 doubles) must fit the staging buffers, the table behind them is being written meanwhile
+    static constexpr int FOLD_MAX_CIN = GTW != 1024 ? 0 : ((STAGE / 8 - 64) / 2 < 1024 ? (STAGE / 8 - 64) / 2 : 1024);
+};
+constexpr int TQ_LDS_WORKGROUP_MAX = 163840;   // what a workgroup may declare on gfx950
+
+template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, bool FUSE, int SCH = 0, bool PW = false, int TBW = 8, int NCB = 2, int GTW = 1024>
 int launch(const ConvArgs& a, hipStream_t stream) {
     using C = Cfg<KT, STRIDE, UPS, WM, WN, SCH, TBW, NCB>;
-    auto kern = conv1d_mfma_kernel<KT, STRIDE, UPS, WM, WN, EPI, ACT, FUSE, SCH, PW, TBW, NCB>;
-    // scheme 2 keeps the folded GroupNorm coefficients of the workgroup's sample behind the staging buffers (2 x C_in floats)
-    constexpr int GTAB_MAX = ((SCH == 2 && ACT >= 1) || (SCH == 0 && TBW == 2 && ACT >= 1 && !PW && EPI == 0)) ? 2 * 4 * 1024 : 0;   // room for C_in <= 1024
-    constexpr int LDS_BYTES = (PW ? 4 * C::BUF : C::LDS_BYTES) + GTAB_MAX;
+    using L = ConvLds<KT, STRIDE, UPS, WM, WN, EPI, ACT, SCH, PW, TBW, NCB, GTW>;
+    auto kern = conv1d_mfma_kernel<KT, STRIDE, UPS, WM, WN, EPI, ACT, FUSE, SCH, PW, TBW, NCB, GTW>;
+    constexpr int GTAB_MAX = L::GTAB_MAX;
+    constexpr int LDS_BYTES = L::BYTES;
+    static_assert(LDS_BYTES <= TQ_LDS_WORKGROUP_MAX, "tile + coefficient table exceed the LDS a workgroup may declare");
+    if (a.cf_st0 && GTW != 1024) return TQ_ERR_SHAPE;   // (the wide-table tiles do not fold: their GroupNorm gets its tq_gn_finalize launch)
     if (GTAB_MAX && a.cf_st0 && a.C0 + a.C1 > 1024) return TQ_ERR_SHAPE;
-    if (SCH == 2 && a.C0 + a.C1 > 1024) return TQ_ERR_SHAPE;
+    // the table is the only width limit of scheme 2: launches without a prologue (data gradients, skip / resampling convs) read none
+    if (SCH == 2 && ACT >= 1 && a.C0 + a.C1 > GTW) return TQ_ERR_SHAPE;
     if (a.cf_st0) {   // consumer-side GroupNorm fold: built into the small tile's forward launches; its scratch (2 C + 64 doubles) must fit the staging buffers
         constexpr bool built = (TBW == 2 && ACT >= 1 && !PW && EPI == 0) || (SCH == 2 && ACT >= 1 && !PW && EPI == 0 && TBW == 8);
         if (!built || (size_t)(2 * (a.C0 + a.C1) + 64) * sizeof(double) > (size_t)(LDS_BYTES - GTAB_MAX)) return TQ_ERR_SHAPE;   // (the table behind them is being written meanwhile)
@@ -1496,6 +1534,7 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
             if (a.flags & TQ_CONV_POLY2) return TQ_ERR_SHAPE;
             if (a.wfmt == TQ_WFMT_F16_MX6) {
                 if (a.C0 % 64 || a.C1 % 64 || a.sC0 % 64 || a.sC1 % 64 || a.C_out % 128) return TQ_ERR_SHAPE;
+                if (conv_wide_table(a)) return conv_launch_fwd_wide(a, KT, ACT, FUSE, s);
                 return launch<KT, STRIDE, UPS, 4, 1, EPI, ACT, FUSE, 2, false, 2>(a, s);
             }
             if (a.wfmt != TQ_WFMT_BF16X3) return TQ_ERR_SHAPE;
@@ -1518,6 +1557,9 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
         }
         if constexpr (STRIDE == 1 && EPI != 1) {
             if (a.C0 % 64 || a.C1 % 64 || a.sC0 % 64 || a.sC1 % 64) return TQ_ERR_SHAPE;
+            if constexpr (UPS == 0 && EPI == 0 && ACT >= 1) {   // more than 1024 concatenated channels under a GroupNorm prologue: conv1d_fwd_wide*.hip
+                if (conv_wide_table(a)) return conv_launch_fwd_wide(a, KT, ACT, FUSE, s);
+            }
             if constexpr (KT == 1 && UPS == 0 && ACT <= 1) {
                 const int cin = a.C0 + a.C1;
                 // TQ_CONV_CH_TILES (round 6; TQDNE_QKV_PW=0 / 1 forces one form everywhere: A/B switch): launch-bound plans take the

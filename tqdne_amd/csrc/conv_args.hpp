@@ -2,6 +2,7 @@
 // and the fp6 block-scale helpers both use.
 #pragma once
 #include "common.hpp"
+#include "../../include/tqdne_hip.h"
 
 namespace tq {
 
@@ -92,6 +93,13 @@ int conv_launch_fwd_k5b(const ConvArgs& a, hipStream_t stream);
 int conv_launch_qkv(const ConvArgs& a, hipStream_t stream);
 int conv_launch_resample(const ConvArgs& a, int ktaps, int stride, hipStream_t stream);
 int conv_launch_dgrad(const ConvArgs& a, int ktaps, hipStream_t stream);
+// conv1d_fwd_wide.hip (k = 5) / conv1d_fwd_wide_k13.hip (k = 1, 3): the fp16 + MX-fp6 forward tiles (256- and 128-channel tiles of 128
+// positions, small tile) with the 2048-entry GroupNorm coefficient table; `act` 1 GN | 2 GN + SiLU | 3 GN + SiLU + dropout
+constexpr int CONV_GTAB_NARROW = 1024, CONV_GTAB_WIDE = 2048;
+inline bool conv_wide_table(const ConvArgs& a) { return a.C0 + a.C1 > CONV_GTAB_NARROW || (a.flags & TQ_CONV_WIDE_TABLE); }
+int conv_launch_fwd_wide(const ConvArgs& a, int ktaps, int act, bool fuse, hipStream_t stream);
+int conv_launch_fwd_wide_k5(const ConvArgs& a, int act, bool fuse, hipStream_t stream);
+int conv_launch_fwd_wide_k13(const ConvArgs& a, int ktaps, int act, hipStream_t stream);
 
 // conv1d_w4.hip (TQDNE_BUILD_EXPERIMENTS builds only): the one-wave-per-SIMD variant of the stride-1 forward launches in the fp16 +
 // MX-fp6 scheme.  Returns TQ_ERR_SHAPE (nothing launched) for a launch it is not built for; the caller then takes the

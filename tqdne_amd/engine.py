@@ -280,6 +280,17 @@ def _check_head_limits(C_in: int, C_out: int, k: int):
             "and <= 64 KB of LDS")
 
 
+def _check_width_limits(name: str, C_in: int, C_out: int):
+    """The width limits of the conv kernels and of the column sums behind their gradients, asked of the library when the plan is built:
+    a model beyond them fails here, naming the layer, not with a launch error in the middle of its first forward or backward."""
+    lib = _lib.load()
+    max_cin, max_cout = lib.tq_conv1d_max_cin(_lib.TQ_WFMT_BF16X3, 0), min(lib.tq_conv1d_max_cout(), lib.tq_colsum_max_channels())
+    if C_in > max_cin or C_out > max_cout:
+        raise NotImplementedError(
+            f"conv {name}: {C_in} -> {C_out} channels; the HIP path takes up to {max_cin} (concatenated) input channels and up to "
+            f"{max_cout} output channels per conv (tensors of up to {max_cin // 2} channels, a qkv projection of 3 x {max_cout // 3})")
+
+
 def shared_range_flag(model, device) -> torch.Tensor:
     """The model's range-guard flag on ``device`` (int32[1]); created on first use."""
     flags = model.__dict__.setdefault("_range_flags", {})
@@ -471,7 +482,8 @@ class UNetEngine:
             pad = site.K // 2
         srcs_c = [s0.C, (s1.C if s1 else 0)] + ([a.C for a in skip[0]] if skip is not None else [])
         k5_act = site.K == 5 and gn is not None and silu and stride == 1 and not upsample and qkv_planes is None
-        wfmt = _lib.forward_wfmt(site.C_out, srcs_c, stride, upsample, fused_skip=skip is not None, k5_act=k5_act) if launch else 0
+        _check_width_limits(site.name, site.C_in, site.C_out)
+        wfmt = _lib.forward_wfmt(site.C_out, srcs_c, stride, upsample, fused_skip=skip is not None, k5_act=k5_act, gn=gn is not None) if launch else 0
         # the small tile where it is built (see SMALL_TILE_B): the ResBlock convs of a small-batch plan
         small = (launch and (self.B <= SMALL_TILE_B or (self.solo and self.B * ((T_out + 127) // 128) <= SMALL_TILE_WGS)) and k5_act
                  and wfmt in (_lib.TQ_WFMT_BF16X3, _lib.TQ_WFMT_F16_MX6) and not GN_FUSE)
@@ -486,8 +498,14 @@ class UNetEngine:
         pend = getattr(self, "_pending_gn", None)
         if pend is not None and gn is not None and pend["key"] == gn[0].data_ptr():
             self._pending_gn = None
+            # (the fold only where the library's tile takes it at this width -- its scratch must fit the tile's staging buffers; a
+            # small-tile conv keeps its fold when the range guard moves it to bf16x3, so that tile's limit binds too)
+            fold_max = self.lib.tq_conv1d_gn_fold_max_cin(wfmt, 32 if small else 0, site.C_out)
+            if small and wfmt != _lib.TQ_WFMT_BF16X3:
+                fold_max = min(fold_max, self.lib.tq_conv1d_gn_fold_max_cin(_lib.TQ_WFMT_BF16X3, 32, site.C_out))
+            fold_fits = site.C_in <= fold_max
             fold_default = (GN_FOLD_DEFAULT and not small and k5_act and wfmt == _lib.TQ_WFMT_F16_MX6 and self.scheme == "auto"
-                            and getattr(self.m, "_conv_scheme", "auto") == "auto")
+                            and getattr(self.m, "_conv_scheme", "auto") == "auto" and fold_fits)
             if fold_default and launch and not self.ckpt and not GN_FUSE:
                 # the tq_gn_finalize launch stays in the plan as a no-op: the range-guard fallback moves this conv to the three-product
                 # scheme, whose default tiles do not fold -- it then gets its launch back (_set_scheme_bf16x3)
@@ -495,7 +513,7 @@ class UNetEngine:
                 self._fold_default_ops = getattr(self, "_fold_default_ops", [])
                 self._fold_default_ops.append((len(self.ops), fn, d))
                 self._emit((_noop_launch, fargs, fname + " (folded into its consumer)", ffl), nbytes=0)
-            if launch and ((small and GN_FOLD_SMALL) or fold_default) and not self.ckpt and not GN_FUSE:
+            if launch and ((small and GN_FOLD_SMALL and fold_fits) or fold_default) and not self.ckpt and not GN_FUSE:
                 f = _lib.TqGnFold()
                 ps0, ps1 = pend["srcs"]
                 f.stats0, f.stats1 = _p(ps0.stats), (_p(ps1.stats) if ps1 is not None else None)
@@ -603,7 +621,7 @@ class UNetEngine:
         d2.ktaps, d2.stride, d2.pad, d2.upsample = 3, 1, 1, 0
         d2.flags = (d.flags & TQ_CONV_STATS) | _lib.TQ_CONV_POLY2
         d2.emb_stride = 0
-        d2.wfmt = _lib.forward_wfmt(2 * Cr, [d.C_in0, d.C_in1])
+        d2.wfmt = _lib.forward_wfmt(2 * Cr, [d.C_in0, d.C_in1], gn=False)
         ps.pack_mode = _lib.PACK_MODE[d2.wfmt]
         self._wfmt_sites.append((d2, [ps], d2.wfmt))
         if d2.flags & TQ_CONV_STATS:
@@ -644,7 +662,7 @@ class UNetEngine:
             d = TqConvDesc()
             d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = 1, B, B, self.E, 0, self.emb_total
             d.ktaps, d.stride, d.pad, d.upsample, d.flags = 1, 1, 0, 0, 0
-            d.wfmt = _lib.forward_wfmt(self.emb_total, [self.E])
+            d.wfmt = _lib.forward_wfmt(self.emb_total, [self.E], gn=False)
             self.emb_pack_mode = _lib.PACK_MODE[d.wfmt]
             self.emb_entry = self.store.entry("emb_packed", lib.tq_conv_weight_pack_bytes(self.emb_total, self.E, 1, self.emb_pack_mode))
             self.emb_packed = self.emb_entry["buf"]

@@ -282,6 +282,8 @@ class BackwardPlan:
         # (and only where the forward scheme requested for the model is the same one: TQDNE_CONV_SCHEME=bf16x3 / f16mx8 means
         # fp32-range three-product data gradients too)
         # (round 6: 64 | C_in through the 64-channel tile -- the 64- and 192-channel inputs of the T = 4096 level -- with TQDNE_DGRAD_MX6_C64=1; measured slower)
+        # (no width limit in either scheme: a data gradient has no GroupNorm prologue, hence no coefficient table -- C_dy = 3072 of a wide
+        # qkv projection and C_dx = 1024 + 1024 of a wide output block run the same tiles)
         cin_ok = site.C_in % 128 == 0 or (site.C_in % 64 == 0 and DGRAD_MX6_C64)
         mx6 = (DGRAD_SCHEME == "f16mx6" and _lib.requested_scheme() == "f16mx6"
                and amax is not None and site.C_out % 64 == 0 and cin_ok

@@ -35,20 +35,26 @@ def pack_conv_weight(w: torch.Tensor, mode: int = 0) -> torch.Tensor:
 
 def conv1d(x0, weight, bias=None, *, x1=None, gscale=None, gshift=None, silu=False, emb=None, residual=None,
            stride=1, upsample=False, stats=True, dropout_p=0.0, dropout_seed=0, dropout_site=0, skip=None, wfmt=None, t_tile=0,
-           gn_fold=None):
+           gn_fold=None, wide_table=False, out=None):
     """x0/x1 (B, T, C) channels-last fp32; weight (C_out, C_in, K) torch layout.  Returns (y, stats|None).
     skip=(sx0, sx1|None, w_skip (C_out, Cs, 1), b_skip|None): fused 1x1 conv of the un-activated sx (tq_conv1d_fwd_skip).
     t_tile=32: the small tile (TqConvDesc.t_tile); the statistics then have one slot per 32 positions.
     gn_fold=(stats0, stats1|None, slot0, slot1, gamma, beta, mean_rstd|None): the launch folds its own GroupNorm (TqConvDesc.gn_fold) and
-    WRITES the coefficients into ``gscale`` / ``gshift`` (pass empty (B, C_in) tensors) and ``mean_rstd``."""
+    WRITES the coefficients into ``gscale`` / ``gshift`` (pass empty (B, C_in) tensors) and ``mean_rstd``.
+    wide_table=True: TQ_CONV_WIDE_TABLE -- the wide-table fp16 + MX-fp6 tile (what more than 1024 concatenated channels get) for a
+    narrower launch too; same bits.  ``out`` = (y, stats | None): caller-owned result buffers."""
     lib = _lib.load()
     B, T_in, C0 = x0.shape
     C1 = 0 if x1 is None else x1.shape[2]
     C_out, C_in, K = weight.shape
     assert C_in == C0 + C1
     T_out = (T_in + 2 * (K // 2) - K) // 2 + 1 if stride == 2 else (2 * T_in if upsample else T_in)
-    y = torch.empty(B, T_out, C_out, device=x0.device)
-    st = torch.empty(B, (T_out + 31) // 32 if t_tile == 32 else nslots(T_out), C_out, 2, device=x0.device) if stats else None
+    if out is not None:
+        y, st = out
+        stats = st is not None
+    else:
+        y = torch.empty(B, T_out, C_out, device=x0.device)
+        st = torch.empty(B, (T_out + 31) // 32 if t_tile == 32 else nslots(T_out), C_out, 2, device=x0.device) if stats else None
     d = TqConvDesc()
     d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, T_in, T_out, C0, C1, C_out
     d.ktaps, d.stride, d.pad, d.upsample = K, stride, K // 2, int(upsample)
@@ -66,13 +72,16 @@ def conv1d(x0, weight, bias=None, *, x1=None, gscale=None, gshift=None, silu=Fal
         f |= TQ_CONV_STATS
     if dropout_p > 0:
         f |= TQ_CONV_DROPOUT
+    if wide_table:
+        f |= _lib.TQ_CONV_WIDE_TABLE
     d.flags = f
     d.emb_stride = 0 if emb is None else emb.stride(0)
     d.dropout_site, d.dropout_p, d.dropout_seed = dropout_site, dropout_p, dropout_seed
     if wfmt is None:
         srcs = [C0, C1] + ([skip[0].shape[2], 0 if skip[1] is None else skip[1].shape[2]] if skip is not None else [])
         wfmt = _lib.forward_wfmt(C_out, srcs, stride, upsample, fused_skip=skip is not None,
-                                 k5_act=K == 5 and gscale is not None and silu and stride == 1 and not upsample and t_tile == 0)
+                                 k5_act=K == 5 and gscale is not None and silu and stride == 1 and not upsample and t_tile == 0,
+                                 gn=gscale is not None)
     d.wfmt = wfmt
     if gn_fold is not None:
         f = _lib.TqGnFold()
@@ -227,7 +236,7 @@ def conv1d_bwd_data(dy, weight, *, x0=None, x1=None, gscale=None, gshift=None, s
 
 
 def conv1d_bwd_weight(dy, x0, wshape, *, x1=None, gscale=None, gshift=None, silu=False, stride=1, upsample=False,
-                      dropout_p=0.0, dropout_seed=0, dropout_site=0, colsum=None):
+                      dropout_p=0.0, dropout_seed=0, dropout_site=0, colsum=None, out=None):
     """weight gradient; ``colsum`` = (per-sample sums (B, C_out) | None, per-channel sums (C_out,) | None): column sums of dy ACCUMULATED
     into those tensors by the same launch (tq_conv1d_bwd_weight_colsum)"""
     lib = _lib.load()
@@ -248,7 +257,7 @@ def conv1d_bwd_weight(dy, x0, wshape, *, x1=None, gscale=None, gshift=None, silu
     d.flags = f
     d.dropout_site, d.dropout_p, d.dropout_seed = dropout_site, dropout_p, dropout_seed
     ws = torch.empty(lib.tq_conv1d_bwd_weight_workspace(C.byref(d)), dtype=torch.uint8, device=dy.device)
-    dw = torch.empty(C_out, C_in, K, device=dy.device)
+    dw = torch.empty(C_out, C_in, K, device=dy.device) if out is None else out   # (``out``: caller-owned (C_out, C_in, K) buffer)
     if colsum is not None:
         bc, c1 = colsum
         check(lib.tq_conv1d_bwd_weight_colsum(C.byref(d), _p(dy), _p(x0), _p(x1), _p(gscale), _p(gshift), _p(dw), _p(ws), ws.numel(),
@@ -280,10 +289,16 @@ def gn_bwd_apply(g, x, coefs, c_total, c_offset=0, r=None, accumulate_into=None)
     return dx
 
 
-def colsum(dy, per_sample=True, total=True, bscale=None, amax=None):
-    """``amax``: optional zeroed int32[TQ_AMAX_WORDS] device block that receives the bit pattern of max|dy| (see amax_bits)"""
+def colsum(dy, per_sample=True, total=True, bscale=None, amax=None, out=None):
+    """``amax``: optional zeroed int32[TQ_AMAX_WORDS] device block that receives the bit pattern of max|dy| (see amax_bits).
+    ``out`` = (per-sample (B, C) | None, total (C,) | None, second total (C,) | None): caller-owned, zeroed destinations (all three of
+    tq_colsum's sums); the same tuple is returned.  Any C with 4 | C (more than 1024 channels are dealt over the grid in chunks)."""
     lib = _lib.load()
     B, T, Cn = dy.shape
+    if out is not None:
+        obc, oc, oc2 = out
+        check(lib.tq_colsum(_p(dy), B, T, Cn, _p(obc), Cn, _p(oc), _p(oc2), _p(bscale), _p(amax), _stream(dy.device)), "colsum")
+        return obc, oc, oc2
     obc = torch.zeros(B, Cn, device=dy.device) if per_sample else None
     oc = torch.zeros(Cn, device=dy.device) if total else None
     check(lib.tq_colsum(_p(dy), B, T, Cn, _p(obc), Cn, _p(oc), None, _p(bscale), _p(amax), _stream(dy.device)), "colsum")
@@ -305,10 +320,18 @@ def amax_value(block) -> float:
     return float(block.max().view(torch.float32).item()) if block.numel() > 1 else float(block.view(torch.float32).item())
 
 
-def gn_bwd_apply_colsum(g, x, coefs, c_total, c_offset=0, r=None, accumulate_into=None, per_sample=True, total=True, amax=None):
-    """tq_gn_bwd_apply_colsum: dx as gn_bwd_apply, plus (per-sample column sums | None, total column sums | None) of dx"""
+def gn_bwd_apply_colsum(g, x, coefs, c_total, c_offset=0, r=None, accumulate_into=None, per_sample=True, total=True, amax=None, out=None):
+    """tq_gn_bwd_apply_colsum: dx as gn_bwd_apply, plus (per-sample column sums | None, total column sums | None) of dx.
+    ``out`` = (dx | None, per-sample | None, total | None, second total | None): caller-owned destinations (the sums zeroed); returned."""
     lib = _lib.load()
     B, T, Cs = g.shape
+    if out is not None:
+        dx, obc, oc, oc2 = out
+        dx = dx if dx is not None else (accumulate_into if accumulate_into is not None else torch.empty_like(g))
+        check(lib.tq_gn_bwd_apply_colsum(_p(g), _p(x), _p(r), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]), _p(dx), B, T, Cs, c_total, c_offset,
+                                         int(accumulate_into is not None), _p(obc), Cs, _p(oc), _p(oc2), _p(amax), _stream(g.device)),
+              "gn_bwd_apply_colsum")
+        return dx, obc, oc, oc2
     dx = accumulate_into if accumulate_into is not None else torch.empty_like(g)
     obc = torch.zeros(B, Cs, device=g.device) if per_sample else None
     oc = torch.zeros(Cs, device=g.device) if total else None
