@@ -69,26 +69,6 @@ typedef struct ihipStream_t* hipStream_t;
  * tq_conv1d_fwd_skip: the 64-channel ResBlock convs; tile of 64 channels x 128 positions). */
 #define TQ_WFMT_F16_MX6 2
 
-/* EXPERIMENT (only in builds with TQ_BUILD_EXPERIMENTS_BIT; otherwise TqConvDesc.gn_fuse is reserved and must be NULL: a non-NULL
- * value returns TQ_ERR_ARG).  GroupNorm finalisation fused into the launch that completes a tensor's statistics (ABI 3).
- * With TQ_CONV_STATS the launch's workgroups publish their partial sums, take an arrival ticket per sample, and the workgroup whose
- * ticket completes sample b folds the statistics of that sample into the scale / shift of the GroupNorm that CONSUMES the produced
- * tensor (what tq_gn_finalize would do in a launch of its own: bit-identical coefficients).  The consumer may normalise the
- * concatenation of the produced tensor with a second, older one (`partner_stats`, complete before this launch).
- * `counters`: device, one uint64 per sample, zero-initialised ONCE by the caller and owned by this (launch site, consumer) pair:
- * tickets count up monotonically, nothing is reset between launches.  Launches using the same TqGnFuse must not overlap. */
-typedef struct TqGnFuse {
-    unsigned long long* counters; /* (B) arrival tickets */
-    const float* partner_stats;   /* (B, nslots, C_partner, 2) or NULL */
-    int32_t C_partner;
-    int32_t partner_first;        /* 1: the consumer's channels are [partner | produced], 0: [produced | partner] */
-    const float* gamma;           /* (C_total) affine parameters of the consuming GroupNorm */
-    const float* beta;
-    float* gscale;                /* (B, C_total) out */
-    float* gshift;                /* (B, C_total) out */
-    float* mean_rstd;             /* (B, 32, 2) out, nullable */
-} TqGnFuse;
-
 /* ABI 7.  Consumer-side GroupNorm fold (TqConvDesc.gn_fold; optional, NULL = off): the launch forms the folded coefficients of ITS OWN
  * prologue (TQ_CONV_GN) from the partial statistics of its (up to two, concatenated) source tensors -- every workgroup folds its sample,
  * the arithmetic of tq_gn_finalize, bit-identical coefficients -- and WRITES them to the gscale / gshift arguments of the call (and
@@ -123,7 +103,7 @@ typedef struct TqConvDesc {
      * read such a tensor un-normalised (fused 1x1 skip convs, up-sampling convs) to TQ_WFMT_BF16X3.  Device pointer, never reset
      * by the library. */
     int32_t* range_flag;
-    const TqGnFuse* gn_fuse; /* reserved, NULL (experiment builds: host pointer, read at launch; see TqGnFuse) */
+    const void* reserved1;   /* reserved, must be NULL: a non-NULL value returns TQ_ERR_ARG */
     /* ABI 5.  Positions per workgroup along T: 0 = the default tiles (128 / 256); 32 = the small tile for launch-bound batches (a
      * launch of the default tiling with far fewer workgroups than compute units: four times the workgroups, a quarter of the work
      * each).  Built for tq_conv1d_fwd / tq_conv1d_fwd_skip with ktaps 5, stride 1, no upsampling, TQ_CONV_GN | TQ_CONV_SILU, in
@@ -165,10 +145,7 @@ typedef struct TqConvBwdDesc {
 } TqConvBwdDesc;
 
 int tq_abi_version(void);
-/* Bit mask of optional parts compiled into this library.  TQ_BUILD_EXPERIMENTS_BIT: the opt-in kernels that lost their A/B
- * (one-wave-per-SIMD conv, slim 64-channel tile, in-launch GroupNorm fold = TqConvDesc.gn_fuse) are present; the default build
- * (`python -m tqdne_amd._build`) leaves them out, `TQDNE_BUILD_EXPERIMENTS=1` builds them into libtqdne_hip_exp.so. */
-#define TQ_BUILD_EXPERIMENTS_BIT 1
+/* Bit mask of optional parts compiled into this library: there are none, always 0 (kept for ABI 5 callers). */
 int tq_build_flags(void);
 
 /* ---- weights -------------------------------------------------------------------------------------------- */

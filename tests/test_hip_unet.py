@@ -572,11 +572,8 @@ def test_inference_forward_matches_backward_capable_forward(which):
     eng2.set_kv_v_format(_lib.TQ_KV_V_BF16)
     b2 = eng2.forward(x, t, cond, infer=True).clone()
     eng2.set_kv_v_format(fmt0)
-    from tqdne_amd import engine as _E
-    if _E.POLY_TRAIN:   # round 6: forwards a backward may follow run the two-phase form too (their gradients are that conv's)
-        assert torch.equal(a2, b2) and 0 < rel_err(a2.cpu(), a.cpu()) < 4e-5
-    else:
-        assert torch.equal(a2, a)
+    # round 6: forwards a backward may follow run the two-phase form too (their gradients are that conv's)
+    assert torch.equal(a2, b2) and 0 < rel_err(a2.cpu(), a.cpu()) < 4e-5
     npoly = sum(op[2].endswith("+polyphase") for op in eng2.ops_infer)
     # (micro at T = 248: the up-sampling conv over 124 rows qualifies since round 5 -- a last tile of more than 64 rows --, the one over 62 does not)
     assert npoly == (3 if which == "paper" else 1)

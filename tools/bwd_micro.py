@@ -89,7 +89,7 @@ for (Cc, T) in [] if ONLY not in ("", "gn") else [(64, 4096), (128, 2048), (256,
                                           None, p(am), stream()) == 0
     print(f"{Cc:4d} x {T:5d}: {med(apply):7.1f} | {med(cs):7.1f} | {med(both):7.1f} | {med(fused):7.1f}   per-sample sums only: colsum {med(cs_rows):7.1f}, fused {med(fused_rows):7.1f}")
 
-print("## stem weight gradient | head backward (3 x 4096, 64 channels)   [TQDNE_STEM_HEAD_BWD=3: round 3's kernels]")
+print("## stem weight gradient | head backward (3 x 4096, 64 channels)")
 if ONLY in ("", "stemhead"):
     T = 4096
     dy = torch.randn(B, T, 64, device=dev); xin = torch.randn(B, 3, T, device=dev); sc = torch.rand(B, device=dev) + 0.5

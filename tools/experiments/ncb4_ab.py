@@ -1,6 +1,6 @@
-"""A/B of the 256-channel conv tile as 4 x 2 waves of 64 channels x 64 positions (TQDNE_CONV_NCB4=1: half the LDS reads per MFMA, one weight
-buffer) against the default 8 x 1 waves of 32 x 128: us per launch and a checksum of output + statistics.
-usage: TQDNE_CONV_NCB4=0|1 python tools/experiments/ncb4_ab.py [B]"""
+"""Per-layer timer of the 256-channel conv tile (written for the A/B of a 4 x 2-wave tile of 64 channels x 64 positions, not kept): us per
+launch and a checksum of output + statistics, for the library named in TQDNE_HIP_LIB.
+usage: [TQDNE_HIP_LIB=...] python tools/experiments/ncb4_ab.py [B]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -45,4 +45,4 @@ for (C0, C1, Co, T) in LAYERS:
     e1.record()
     torch.cuda.synchronize()
     cs = int(y.view(torch.int32).to(torch.int64).sum()) ^ int(st.view(torch.int32).to(torch.int64).sum())
-    print(f"NCB4={os.environ.get('TQDNE_CONV_NCB4', '0')} B={B} {C0}+{C1}->{Co} T={T} wfmt={d_wfmt}: {1e3 * e0.elapsed_time(e1) / n:7.1f} us  checksum {cs & 0xFFFFFFFFFFFF:012x}", flush=True)
+    print(f"B={B} {C0}+{C1}->{Co} T={T} wfmt={d_wfmt}: {1e3 * e0.elapsed_time(e1) / n:7.1f} us  checksum {cs & 0xFFFFFFFFFFFF:012x}", flush=True)

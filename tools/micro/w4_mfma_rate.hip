@@ -1,4 +1,4 @@
-// How fast does ONE wave per SIMD issue the MFMA stream of conv1d_w4.hip (4 x fp16, 4 x fp16, 4 x block-scaled fp6 per step, operands
+// How fast does ONE wave per SIMD issue the MFMA stream of the one-wave-per-SIMD conv experiment (not kept) (4 x fp16, 4 x fp16, 4 x block-scaled fp6 per step, operands
 // in registers, nothing else in the loop)?  Prints shader cycles per MFMA for: A operands in AccVGPRs / in VGPRs, with / without the
 // scaled MFMAs, 1 or 2 waves per SIMD.   hipcc --offload-arch=gfx950 -O3 w4_mfma_rate.hip -o w4_mfma_rate && ./w4_mfma_rate
 #include <hip/hip_runtime.h>

@@ -65,7 +65,7 @@ def conv_max_cin(wfmt: int, C_out: int = 0) -> int:
     return load().tq_conv1d_max_cin(wfmt, C_out)
 
 
-def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, fused_skip: bool = False, k5_act: bool = False,
+def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, k5_act: bool = False,
                  gn: Optional[bool] = None) -> int:
     """Contraction scheme of a forward conv launch (include/tqdne_hip.h, TQ_WFMT_*): fp16 + block-scaled corrections where the kernel
     is built for the shape (stride 1 incl. the nearest-upsampling convs, 128 | C_out, 64 | every source's channels incl. a fused skip
@@ -75,8 +75,6 @@ def forward_wfmt(C_out: int, sources, stride: int = 1, upsample: bool = False, f
     v = requested_scheme()
     co_ok = C_out % 128 == 0 or (C_out % 64 == 0 and k5_act and not upsample and v == "f16mx6" and MX6_C64)
     ok = stride == 1 and co_ok and all(c % 64 == 0 for c in sources if c)
-    if fused_skip:
-        ok = ok and os.environ.get("TQDNE_FUSED_SKIP_MX8", "1") != "0"
     if not ok or v == "bf16x3":
         return TQ_WFMT_BF16X3
     fmt = TQ_WFMT_F16_MX6 if v == "f16mx6" else TQ_WFMT_F16_MX8
@@ -94,12 +92,6 @@ TQ_AMAX_WAYS, TQ_AMAX_STRIDE = 16, 32           # include/tqdne_hip.h: max|dy| b
 TQ_AMAX_WORDS = TQ_AMAX_WAYS * TQ_AMAX_STRIDE
 
 
-class TqGnFuse(C.Structure):
-    _fields_ = [("counters", C.c_void_p), ("partner_stats", C.c_void_p), ("C_partner", C.c_int32), ("partner_first", C.c_int32),
-                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("gscale", C.c_void_p), ("gshift", C.c_void_p),
-                ("mean_rstd", C.c_void_p)]
-
-
 class TqGnFold(C.Structure):
     _fields_ = [("stats0", C.c_void_p), ("stats1", C.c_void_p), ("slot0", C.c_int32), ("slot1", C.c_int32),
                 ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean_rstd", C.c_void_p)]
@@ -113,7 +105,7 @@ class TqConvDesc(C.Structure):
         ("upsample", C.c_int32), ("flags", C.c_int32), ("emb_stride", C.c_int32),
         ("dropout_site", C.c_uint32), ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64),
         ("C_skip0", C.c_int32), ("C_skip1", C.c_int32), ("wfmt", C.c_int32),
-        ("range_flag", C.c_void_p), ("gn_fuse", C.POINTER(TqGnFuse)), ("t_tile", C.c_int32), ("reserved2", C.c_int32),
+        ("range_flag", C.c_void_p), ("reserved1", C.c_void_p), ("t_tile", C.c_int32), ("reserved2", C.c_int32),
         ("gn_fold", C.POINTER(TqGnFold)),
     ]
 
@@ -221,19 +213,9 @@ _PROTOS = {
     "tq_head_conv_bwd_ws": (I, [VP] * 10 + [I] * 5 + [VP, SZ, VP]),
 }
 
-# entry points of later rounds are optional at load time but listed in the header check
-_OPTIONAL = {}
-
-
 def lib_path() -> str:
     # TQDNE_HIP_LIB: developer override used by tools/ to A/B kernel variants; the default is the in-tree build
-    # (TQDNE_BUILD_EXPERIMENTS=1: the build that also holds the opt-in kernels, libtqdne_hip_exp.so)
-    return os.environ.get("TQDNE_HIP_LIB", _build.EXP_LIBPATH if _build.EXPERIMENTS else _build.LIBPATH)
-
-
-def has_experiments() -> bool:
-    """True when the loaded library was built with the opt-in kernels (conv1d_w4, slim tile, in-launch GroupNorm fold)."""
-    return bool(load().tq_build_flags() & 1)
+    return os.environ.get("TQDNE_HIP_LIB", _build.LIBPATH)
 
 
 def load():
@@ -252,11 +234,6 @@ def load():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: loud
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in _OPTIONAL.items():
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
     if lib.tq_abi_version() != ABI_VERSION:
         raise RuntimeError("libtqdne_hip.so ABI version mismatch")
     _LIB = lib
@@ -264,7 +241,7 @@ def load():
 
 
 def exported_symbols():
-    return sorted(list(_PROTOS) + list(_OPTIONAL))
+    return sorted(_PROTOS)
 
 
 class TqError(RuntimeError):

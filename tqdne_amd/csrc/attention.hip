@@ -263,12 +263,11 @@ int launch_attn(const float* qkv, float* out, float* lse, int B, int T, int H, h
     const int nqt = (T + QT - 1) / QT, nkt = (T + KTILE - 1) / KTILE;
     const float scale = (float)(1.0 / sqrt(sqrt((double)D)));  // blocks.py:173 (python double, then fp32)
     // key split (needs the workspace): where the grid would leave most of the chip idle -- under 128 workgroups for 256 compute units
-    // -- deal the key tiles over as many workgroups as bring it to ~256 (TQDNE_ATTN_KSPLIT: 1 = never, n = that many where allowed)
-    static const int forced = [] { const char* e = getenv("TQDNE_ATTN_KSPLIT"); return e ? atoi(e) : 0; }();
+    // -- deal the key tiles over as many workgroups as bring it to ~256
     int ksplit = 1;
     const int wgs = B * H * nqt;
-    if (workspace && (forced > 1 || (forced == 0 && wgs < 128))) {
-        ksplit = forced > 1 ? forced : 256 / wgs;
+    if (workspace && wgs < 128) {
+        ksplit = 256 / wgs;
         if (ksplit > nkt) ksplit = nkt;
         if (ksplit > ATT_KSPLIT_MAX) ksplit = ATT_KSPLIT_MAX;
         if (ksplit < 1) ksplit = 1;
@@ -414,9 +413,6 @@ __global__ __launch_bounds__(256, 2) void attention_fwd2_kernel(const float* __r
     if (tid == 0 && blockIdx.x < 4096) tq_att_timeline[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memtime();
 #endif
     ATT_T(0)
-#ifdef TQ_ATT_SKEW
-    if ((blockIdx.x >> 8) & 1) { for (int i = 0; i < TQ_ATT_SKEW; ++i) __builtin_amdgcn_s_sleep(16); }
-#endif
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
     const int nqt = (T + 64 * ATT_QB - 1) / (64 * ATT_QB);

@@ -25,13 +25,11 @@ constexpr size_t dq_lds_bytes(int D) { return (size_t)4 * 64 * (D * 2 + 16) + 4 
 constexpr size_t dkv_lds_bytes(int D, int QB) { return (size_t)4 * QB * (D * 2 + 16) + 128 * sizeof(float) + 4 * 4 * 16 * (QB * 2 + 16); }
 
 // key split of the forward (needs the workspace): where the grid would leave most of the chip idle -- under 128 workgroups for 256
-// compute units -- deal the key tiles over as many workgroups as bring it to ~256 (TQDNE_ATTN_KSPLIT: 1 = never, n = that many where
-// allowed)
+// compute units -- deal the key tiles over as many workgroups as bring it to ~256
 inline int key_split(int wgs, int nkt, const void* workspace) {
-    static const int forced = [] { const char* e = getenv("TQDNE_ATTN_KSPLIT"); return e ? atoi(e) : 0; }();
     int ksplit = 1;
-    if (workspace && (forced > 1 || (forced == 0 && wgs < 128))) {
-        ksplit = forced > 1 ? forced : 256 / wgs;
+    if (workspace && wgs < 128) {
+        ksplit = 256 / wgs;
         if (ksplit > nkt) ksplit = nkt;
         if (ksplit > ATT_KSPLIT_MAX) ksplit = ATT_KSPLIT_MAX;
         if (ksplit < 1) ksplit = 1;

@@ -14,20 +14,6 @@ namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-// -DTQ_WG_ABL_HIHI (timing ablation, wrong numerics, never in the shipped library): the weight gradient's products with the two
-// first-order terms dropped (ONE bf16 MFMA per product instead of three) = the bound of any cheaper contraction scheme for it;
-// -DTQ_WG_ABL_HALF: two of the three (the MFMA cycles an fp16 + MX-fp6 port would execute: 1.5 units, here as 2)
-__device__ __forceinline__ f32x4 wg_mma(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 c) {
-#if defined(TQ_WG_ABL_HIHI)
-    return mfma_bf16(ah, bh, c);
-#elif defined(TQ_WG_ABL_HALF)
-    c = mfma_bf16(ah, bl, c);
-    return mfma_bf16(ah, bh, c);
-#else
-    return mfma_x3(ah, al, bh, bl, c);
-#endif
-}
-
 // ds_read_b64_tr_b16: per 16-lane group, lane 4q+p supplies the address of (row q, cols 4p..4p+3); lane i receives
 // column i of rows 0..3.  Two reads (rows +0, +4) give the 8 consecutive k of one MFMA operand fragment.
 __device__ __forceinline__ uint2 lds_tr_read(const unsigned char* p) {
@@ -312,7 +298,6 @@ __global__ __launch_bounds__((W8 && !H64) ? 512 : 256, (W8 && !H64) ? 1 : 2) voi
             al[mb].h[1] = lds_tr_read(dy_lo + off4);
         }
     };
-#if !defined(TQ_WG_OLD_COMPUTE)
     // Round 4.  The compute phase ran at 2.2x its MFMA time with staging and loads ablated (tools/bwd_micro.py, -DTQ_WG_ABL_*): per
     // (tap, channel block) step hipcc issued the four transposed reads of the xhat fragment right in front of the six MFMAs that
     // consume them -- an LDS round trip exposed twenty times per unit.  For the stride-1 convs the taps are row shifts of ONE image, so
@@ -363,15 +348,12 @@ __global__ __launch_bounds__((W8 && !H64) ? 512 : 256, (W8 && !H64) ? 1 : 2) voi
                     tap_frag(w.l, ol, k, bl);
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb)
-                        acc[mb][nb][k] = wg_mma(ah[mb].v, al[mb].v, bh.v, bl.v, acc[mb][nb][k]);
+                        acc[mb][nb][k] = mfma_x3(ah[mb].v, al[mb].v, bh.v, bl.v, acc[mb][nb][k]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
             return;
         }
-#else
-    auto compute = [&]() __attribute__((always_inline)) {
-#endif
 #pragma unroll (NCI == 2 && KT == 5 ? 1 : 2)
         for (int ks = 0; ks < WG_TT / 32; ++ks) {
             const int r0 = ks * 32 + 8 * g + q;  // reduction row supplied by this lane (first read; +4 second)
@@ -391,7 +373,7 @@ __global__ __launch_bounds__((W8 && !H64) ? 512 : 256, (W8 && !H64) ? 1 : 2) voi
                     bl.h[1] = lds_tr_read(x_lo + off4);
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb)
-                        acc[mb][nb][k] = wg_mma(ah[mb].v, al[mb].v, bh.v, bl.v, acc[mb][nb][k]);
+                        acc[mb][nb][k] = mfma_x3(ah[mb].v, al[mb].v, bh.v, bl.v, acc[mb][nb][k]);
                 }
             }
         }
@@ -498,31 +480,27 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 int wgrad_nci(const TqConvDesc* d) {
-    // 64-channel chunks where both concat sources are made of whole chunks (every 1-D config: 64 | C); TQDNE_WGRAD_NCI=1 forces 32
-    static const int forced = [] { const char* e = getenv("TQDNE_WGRAD_NCI"); return e ? atoi(e) : 0; }();
-    if (forced == 1) return 1;
+    // 64-channel chunks where both concat sources are made of whole chunks (every 1-D config: 64 | C)
     // Measured (B = 64, paper UNet): the ResBlocks' 1x1 skip convs gain 15-29 % from the 64-channel chunk (their MFMA phase is a
     // fifth of a k = 5 one, so the dy staging dominates); k = 5 loses 35-50 % (160 accumulator registers: 17 spills and no room
     // for the staging prefetch), k = 3 loses 16-34 %, the attention projections are neutral -> 64 only for k = 1
-    if (d->ktaps != 1 && forced != 2) return 1;
+    if (d->ktaps != 1) return 1;
     // round 5: 128-channel chunks for the 1x1 convs whose sources are made of whole ones (dy is then staged C_in / 128 times)
-    if (d->ktaps == 1 && d->stride == 1 && !d->upsample && forced != 2 && d->C_in0 % 128 == 0 && d->C_in1 % 128 == 0) return 4;
+    if (d->stride == 1 && !d->upsample && d->C_in0 % 128 == 0 && d->C_in1 % 128 == 0) return 4;
     return (d->C_in0 % 64 == 0 && d->C_in1 % 64 == 0) ? 2 : 1;
 }
 
 // The 8-wave form (W8, see wgrad_kernel) serves the k = 3 / k = 5 launches whose sources are made of whole 64-channel chunks and whose
-// output channels fill the 128-channel tile; TQDNE_WGRAD_W8=0 keeps round 3's 4-wave kernel everywhere.
+// output channels fill the 128-channel tile.
 bool wgrad_w8(const TqConvDesc* d) {
-    static const int sw = [] { const char* e = getenv("TQDNE_WGRAD_W8"); return e ? atoi(e) : 1; }();
-    if (!sw || d->ktaps == 1) return false;
+    if (d->ktaps == 1) return false;
     return d->C_in0 % 64 == 0 && d->C_in1 % 64 == 0 && d->C_out % 128 == 0;
 }
 
 // The four-wave form of the W8 layout for convs with exactly 64 output channels (H64, see wgrad_kernel): k = 3 / k = 5, stride 1, sources
-// made of whole 64-channel chunks; TQDNE_WGRAD_H64=0 keeps the 128-channel tile for them (A/B switch).
+// made of whole 64-channel chunks.
 bool wgrad_h64(const TqConvDesc* d) {
-    static const int sw = [] { const char* e = getenv("TQDNE_WGRAD_H64"); return e ? atoi(e) : 1; }();
-    if (!sw || d->ktaps == 1 || d->stride != 1 || d->upsample) return false;
+    if (d->ktaps == 1 || d->stride != 1 || d->upsample) return false;
     return d->C_in0 % 64 == 0 && d->C_in1 % 64 == 0 && d->C_out == 64;
 }
 
@@ -584,8 +562,7 @@ void wgrad_plan(const TqConvDesc* d, bool wide, int& n_cotiles, int& n_cichunks,
     n_ttiles = (d->T_out + WG_TT - 1) / WG_TT;
     const int U = d->B * n_ttiles;
     const int ntiles = n_cotiles * n_cichunks;
-    static const int forced = [] { const char* e = getenv("TQDNE_WGRAD_SLOTS"); return e ? atoi(e) : 0; }();   // (A/B switch)
-    const int slots = forced > 0 ? forced : wgrad_slots(d, nci, w8, h64);
+    const int slots = wgrad_slots(d, nci, w8, h64);
     int want = slots / ntiles;   // splits per output tile: the grid fills one round of resident workgroups, not more
     if (want < 1) want = 1;
     if (want > U) want = U;
@@ -1088,8 +1065,7 @@ extern "C" int tq_gn_bwd_finalize(const float* gstats, const float* mean_rstd, c
     if (!gstats || !mean_rstd || !gamma || !coef_a || !coef_b || !coef_c || !dgamma || !dbeta) return TQ_ERR_ARG;
     if (B <= 0 || T <= 0 || C <= 0 || C % GN_GROUPS) return TQ_ERR_SHAPE;
     const int nslots = (T + STAT_SLOT - 1) / STAT_SLOT;
-    static const int forced = [] { const char* e = getenv("TQDNE_GNBWD_PARTS"); return e ? atoi(e) : 0; }();   // (A/B switch: 1 = round 3's grid)
-    const int NP = (forced == 1 || forced == 2 || forced == 4 || forced == 8) ? forced : 4;   // 32 / NP whole groups per block
+    const int NP = 4;   // 32 / NP whole groups per block
     const int Cb = C / NP;
     int nsub = Cb <= 128 ? 256 / Cb : 1;   // (as in the kernel)
     if (nsub > nslots) nsub = nslots;
@@ -1112,23 +1088,19 @@ extern "C" int tq_gn_bwd_apply(const float* g, const float* x, const float* r, c
     return 0;
 }
 
-// Tiling of the column-sum kernels (colsum_kernel, gn_bwd_apply_cs_kernel): NT threads per workgroup, `rows` rows of one sample per
-// workgroup -- as many rows as still leaves `min_wgs` workgroups.  A/B switches: TQDNE_COLSUM_THREADS (256 | 1024), TQDNE_COLSUM_ROWS,
-// TQDNE_COLSUM_WGS.
-struct CsTiling { int nt, rows; };
+// Tiling of the column-sum kernels (colsum_kernel, gn_bwd_apply_cs_kernel): CS_NT threads per workgroup, `rows` rows of one sample per
+// workgroup -- as many rows as still leaves `min_wgs` workgroups.
+constexpr int CS_NT = 256;
+struct CsTiling { int rows; };
 static CsTiling colsum_tiling(int B, int T) {
-    static const int f_nt = [] { const char* e = getenv("TQDNE_COLSUM_THREADS"); return e ? atoi(e) : 0; }();
-    static const int f_rows = [] { const char* e = getenv("TQDNE_COLSUM_ROWS"); return e ? atoi(e) : 0; }();
-    static const int f_wgs = [] { const char* e = getenv("TQDNE_COLSUM_WGS"); return e ? atoi(e) : 0; }();
     CsTiling t;
-    t.nt = f_nt == 1024 ? 1024 : 256;
-    // (measured, tools/bwd_micro.py with the switches above, B = 64: 256 workgroups of 256 threads beat 512 / 1024 / 2048 and the
+    // (measured, tools/bwd_micro.py, B = 64: 256 workgroups of 256 threads beat 512 / 1024 / 2048 and the
     // 1024-thread form on every level -- fused apply 47 us next to 44 us for the plain apply; each workgroup ends in C atomic adds, and
     // the total sums' addresses are shared by ALL workgroups)
-    const size_t min_wgs = f_wgs > 0 ? (size_t)f_wgs : 256;
+    const size_t min_wgs = 256;
     int rpw = STAT_SLOT;
     while (rpw < 4096 && (size_t)B * ((T + 2 * rpw - 1) / (2 * rpw)) >= min_wgs) rpw <<= 1;
-    t.rows = f_rows > 0 ? f_rows : rpw;
+    t.rows = rpw;
     return t;
 }
 
@@ -1152,21 +1124,15 @@ extern "C" int tq_colsum(const float* dy, int B, int T, int C, float* out_bc, in
     if (C > CS_CHUNK) {
         int nch;
         const int cw = colsum_chunk_width(C, nch);
-        const size_t shw = (size_t)(tl.nt > cw / 4 ? tl.nt : cw / 4) * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
-        if (tl.nt == 1024)
-            hipLaunchKernelGGL(colsum_chunk_kernel<1024>, dim3(B * nsl, nch), dim3(1024), shw, stream, dy, T, C, cw, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
-        else
-            hipLaunchKernelGGL(colsum_chunk_kernel<256>, dim3(B * nsl, nch), dim3(256), shw, stream, dy, T, C, cw, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
+        const size_t shw = (size_t)(CS_NT > cw / 4 ? CS_NT : cw / 4) * 4 * sizeof(float) + (CS_NT / 64) * sizeof(unsigned);
+        hipLaunchKernelGGL(colsum_chunk_kernel<CS_NT>, dim3(B * nsl, nch), dim3(CS_NT), shw, stream, dy, T, C, cw, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
         TQ_CHECK_LAUNCH();
         return 0;
     }
     const int c4n = C / 4;
-    const int nrow = tl.nt / c4n > 0 ? tl.nt / c4n : 1;
-    const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
-    if (tl.nt == 1024)
-        hipLaunchKernelGGL(colsum_kernel<1024>, dim3(B * nsl), dim3(1024), sh, stream, dy, T, C, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
-    else
-        hipLaunchKernelGGL(colsum_kernel<256>, dim3(B * nsl), dim3(256), sh, stream, dy, T, C, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
+    const int nrow = CS_NT / c4n > 0 ? CS_NT / c4n : 1;
+    const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (CS_NT / 64) * sizeof(unsigned);
+    hipLaunchKernelGGL(colsum_kernel<CS_NT>, dim3(B * nsl), dim3(CS_NT), sh, stream, dy, T, C, out_bc, bc_stride, out_c, out_c2, bscale, amax_out, tl.rows);
     TQ_CHECK_LAUNCH();
     return 0;
 }
@@ -1185,25 +1151,17 @@ extern "C" int tq_gn_bwd_apply_colsum(const float* g, const float* x, const floa
     if (C_src > CS_CHUNK) {
         int nch;
         const int cw = colsum_chunk_width(C_src, nch);
-        const size_t shw = (size_t)(tl.nt > cw / 4 ? tl.nt : cw / 4) * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
-        if (tl.nt == 1024)
-            hipLaunchKernelGGL(gn_bwd_apply_cs_chunk_kernel<1024>, dim3(B * nsl, nch), dim3(1024), shw, stream, g, x, r, coef_a, coef_b, coef_c, dx, T,
-                               C_src, cw, C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
-        else
-            hipLaunchKernelGGL(gn_bwd_apply_cs_chunk_kernel<256>, dim3(B * nsl, nch), dim3(256), shw, stream, g, x, r, coef_a, coef_b, coef_c, dx, T,
-                               C_src, cw, C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
+        const size_t shw = (size_t)(CS_NT > cw / 4 ? CS_NT : cw / 4) * 4 * sizeof(float) + (CS_NT / 64) * sizeof(unsigned);
+        hipLaunchKernelGGL(gn_bwd_apply_cs_chunk_kernel<CS_NT>, dim3(B * nsl, nch), dim3(CS_NT), shw, stream, g, x, r, coef_a, coef_b, coef_c, dx, T,
+                           C_src, cw, C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
         TQ_CHECK_LAUNCH();
         return 0;
     }
     const int c4n = C_src / 4;
-    const int nrow = tl.nt / c4n > 0 ? tl.nt / c4n : 1;
-    const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (tl.nt / 64) * sizeof(unsigned);
-    if (tl.nt == 1024)
-        hipLaunchKernelGGL(gn_bwd_apply_cs_kernel<1024>, dim3(B * nsl), dim3(1024), sh, stream, g, x, r, coef_a, coef_b, coef_c, dx, T, C_src,
-                           C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
-    else
-        hipLaunchKernelGGL(gn_bwd_apply_cs_kernel<256>, dim3(B * nsl), dim3(256), sh, stream, g, x, r, coef_a, coef_b, coef_c, dx, T, C_src,
-                           C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
+    const int nrow = CS_NT / c4n > 0 ? CS_NT / c4n : 1;
+    const size_t sh = (size_t)nrow * c4n * 4 * sizeof(float) + (CS_NT / 64) * sizeof(unsigned);
+    hipLaunchKernelGGL(gn_bwd_apply_cs_kernel<CS_NT>, dim3(B * nsl), dim3(CS_NT), sh, stream, g, x, r, coef_a, coef_b, coef_c, dx, T, C_src,
+                       C_total, c_offset, accumulate, colsum_bc, bc_stride, colsum_c, colsum_c2, amax_out, tl.rows);
     TQ_CHECK_LAUNCH();
     return 0;
 }
@@ -1639,15 +1597,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 }
 }  // namespace
 
-// up to STEM_HEAD_WGS_MAX workgroups x <= 1024 partial sums.  Workgroups per launch (A/B switch TQDNE_STEM_HEAD_WGS), measured at B = 64
+// up to STEM_HEAD_WGS_MAX workgroups x <= 1024 partial sums.  Workgroups per launch (STEM_WGRAD_WGS, HEAD_BWD_WGS), measured at B = 64
 // (tools/bwd_micro.py, us for 256 / 512 / 1024 / 2048): stem weight gradient 118 / 74 / 62 / 86 (118 registers: four workgroups per CU
 // cover each other's staging and load latencies), head backward 102 / 85 / 105 / 145 (157 registers: two per CU).
-constexpr int STEM_HEAD_WGS_MAX = 2048;
-static int stem_head_wgs(int dflt) {
-    static const int forced = [] { const char* e = getenv("TQDNE_STEM_HEAD_WGS"); return e ? atoi(e) : 0; }();
-    const int v = forced > 0 ? forced : dflt;
-    return v > STEM_HEAD_WGS_MAX ? STEM_HEAD_WGS_MAX : v;
-}
+constexpr int STEM_HEAD_WGS_MAX = 2048, STEM_WGRAD_WGS = 1024, HEAD_BWD_WGS = 512;
 extern "C" size_t tq_stem_head_bwd_workspace(void) { return (size_t)STEM_HEAD_WGS_MAX * 1024 * sizeof(float); }
 
 extern "C" int tq_stem_conv_bwd_weight(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in,
@@ -1663,10 +1616,9 @@ extern "C" int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, c
     const size_t sh = ((size_t)C_in * (STAT_SLOT + ktaps - 1) + (size_t)STAT_SLOT * (C_out + 1)) * sizeof(float);
     if (sh > 160 * 1024) return TQ_ERR_SHAPE;
     if (C_out * C_in * ktaps > 8 * 256) return TQ_ERR_SHAPE;
-    static const bool old_form = [] { const char* e = getenv("TQDNE_STEM_HEAD_BWD"); return e && atoi(e) == 3; }();   // (A/B switch: 3 = round 3's kernels)
-    if (!old_form && C_in <= 8 && C_out >= 32 && C_out <= 256 && 256 % C_out == 0 && ktaps == 5) {   // the streaming form (round 4)
+    if (C_in <= 8 && C_out >= 32 && C_out <= 256 && 256 % C_out == 0 && ktaps == 5) {   // the streaming form (round 4)
         const int nunits2 = B * nslots;
-        const int nwg2 = nunits2 < stem_head_wgs(1024) ? nunits2 : stem_head_wgs(1024);
+        const int nwg2 = nunits2 < STEM_WGRAD_WGS ? nunits2 : STEM_WGRAD_WGS;
         const int upw2 = (nunits2 + nwg2 - 1) / nwg2;
         const unsigned grid2 = (unsigned)((nunits2 + upw2 - 1) / upw2);
         const int nout2 = C_out * C_in * 5;
@@ -1712,11 +1664,10 @@ extern "C" int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, c
     if (B <= 0 || T <= 0 || C_in < 8 || C_in % 8 || 256 % (C_in / 4) || C_out < 1 || C_out > 16) return TQ_ERR_SHAPE;
     const int maxco = C_out <= 4 ? 4 : 16;
     const int nslots = (T + STAT_SLOT - 1) / STAT_SLOT;
-    static const bool old_form = [] { const char* e = getenv("TQDNE_STEM_HEAD_BWD"); return e && atoi(e) == 3; }();   // (A/B switch: 3 = round 3's kernels)
-    if (!old_form && C_out <= 8 && ktaps == 5 && C_in >= 32 && C_in <= 256 && 256 % C_in == 0) {   // the streaming form (round 4; 5 ... 8 channels: round 5)
+    if (C_out <= 8 && ktaps == 5 && C_in >= 32 && C_in <= 256 && 256 % C_in == 0) {   // the streaming form (round 4; 5 ... 8 channels: round 5)
         const int mco = C_out <= 4 ? 4 : 8;
         const int nunits = B * nslots;
-        const int nwg = nunits < stem_head_wgs(512) ? nunits : stem_head_wgs(512);
+        const int nwg = nunits < HEAD_BWD_WGS ? nunits : HEAD_BWD_WGS;
         const int upw = (nunits + nwg - 1) / nwg;
         const size_t sh2 = ((size_t)mco * (STAT_SLOT + 4) + (size_t)256 * mco * 5) * sizeof(float);   // (<= 45 KB)
         const unsigned grid2 = (unsigned)((nunits + upw - 1) / upw);

@@ -84,9 +84,8 @@ namespace {
 //      instead of 16 per 64 channels) and the corrections no longer clamp (fp8 with uniform scales saturates beyond |x| = 448 and
 //      |x_l| = 0.109): measured 5e-5 against 7e-4 of the output scale on heavy-tailed data (tools/micro/fp6_scheme_probe.hip).
 //      Staging layout: a thread owns 16 consecutive channels of a row (= exactly one lane fragment of the correction operand).
-// TBW: 16-position blocks per wave along t (8, or 4 for the "slim" 64-channel tile: half the accumulators, so that three or four
-// workgroups share a CU and their load / MFMA / store phases interleave -- see dispatch_tile)
-// NCB: 16-channel blocks per wave (2; 4 for the round-4 tile whose waves are 64 channels x 64 positions, see conv1d_mfma_kernel)
+// TBW: 16-position blocks per wave along t (8; 4 for the 64-channel fp16 + MX-fp6 tile, 2 for the small tile -- see dispatch_tile)
+// NCB: 16-channel blocks per wave (always 2)
 template <int KT, int STRIDE, int UPS, int WM, int WN, int SCH = 0, int TBW = 8, int NCB = 2>
 struct Cfg {
     static constexpr int CH = SCH ? 64 : 32;     // channels per chunk
@@ -129,27 +128,21 @@ struct Cfg {
 // instantiation takes.  1024 (one float4 of either array per thread of a 256-thread workgroup) is every established kernel; 2048 (two) is
 // instantiated for the forward tiles in conv1d_fwd_wide*.hip and reached only when C_in > 1024 (dispatch_tile).
 template <int KT, int STRIDE, int UPS, int WM, int WN, int EPI, int ACT, bool FUSE, int SCH, bool PW = false, int TBW = 8, int NCB = 2, int GTW = 1024>
-__global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ? 3 : 2)) void conv1d_mfma_kernel(const ConvArgs p) {
+__global__ __launch_bounds__(64 * WM * WN, 2) void conv1d_mfma_kernel(const ConvArgs p) {
     static_assert(GTW == 1024 || (GTW == 2048 && SCH == 2 && ACT >= 1 && EPI == 0 && !PW && STRIDE == 1 && UPS == 0 && WN == 1 && NCB == 2 && (TBW == 8 || TBW == 2)),
                   "wide coefficient table: the fp16 + MX-fp6 forward tiles of 128 and 32 positions");
     static_assert(SCH == 0 || STRIDE == 1, "the fp16-range schemes serve stride-1 launches");
     static_assert(EPI != 1 || SCH == 0 || (SCH == 2 && ACT == 0 && !FUSE && !PW), "data gradients: bf16x3, or fp16 + MX-fp6 on a dy scaled into the fp16 range");
-    // NCB == 4 (round 4): 256 channels x 128 positions as 4 x 2 waves of 64 channels x 64 positions -- every activation fragment read
-    // from LDS feeds twelve MFMAs instead of six (tools/micro/mfma_shape_power.hip: at full load the conv's 4 ds_read_b128 per 6 MFMAs
-    // cost a quarter of the matrix rate; 16 reads + 16 weight loads per 48 MFMAs run 13 % faster than 32 + 8)
-    static_assert(NCB == 2 || (NCB == 4 && TBW == 4 && WM == 4 && WN == 2 && SCH == 2 && KT > 1 && STRIDE == 1 && UPS == 0 && EPI == 0 && !FUSE && !PW),
-                  "64-channel waves: the fp16 + MX-fp6 forward tile of 256 x 128");
+    static_assert(NCB == 2, "waves are 32 channels wide");
     // C64 (round 6): the fp16 + MX-fp6 tile of the 64-channel layers -- 64 channels x 128 positions as 2 x 2 waves of 32 channels x 64
     // positions, two workgroups per CU (the 64-channel ResBlock convs at T = 4096 and the data gradients whose input-channel count is a
     // multiple of 64 but not of 128 ran in bf16x3: twice the matrix work)
     constexpr bool C64 = TBW == 4 && NCB == 2 && SCH == 2 && WM == 2 && WN == 2;
     static_assert(!C64 || (STRIDE == 1 && UPS == 0 && !PW && EPI != 2), "64-channel fp16 + MX-fp6 tile: stride-1 forward and data-gradient launches");
-    static_assert(TBW == 8 || (TBW == 4 && NCB == 4) || C64 || (TBW == 4 && SCH == 0 && STRIDE == 1 && UPS == 0 && EPI == 0 && WN == 2 && !PW) ||
-                  (TBW == 2 && (SCH == 0 || (SCH == 2 && WM == 4)) && STRIDE == 1 && UPS == 0 && EPI == 0 && WN == 1 && !PW),
-                  "slim tile: bf16x3 forward, 2 x 2 waves; small tile (32 positions per workgroup): stride-1 forward, one wave column");
+    static_assert(TBW == 8 || C64 || (TBW == 2 && (SCH == 0 || (SCH == 2 && WM == 4)) && STRIDE == 1 && UPS == 0 && EPI == 0 && WN == 1 && !PW),
+                  "small tile (32 positions per workgroup): stride-1 forward, one wave column");
     static_assert(!PW || (KT == 1 && STRIDE == 1 && UPS == 0 && SCH >= 1 && !FUSE && WN == 1 && EPI != 1), "PW: 1x1, fp16-range schemes");
-    static_assert(SCH != 2 || WN == 1 || NCB == 4 || C64 || (WN == 2 && WM == 4 && TBW == 8 && STRIDE == 1 && UPS == 0 && EPI == 0 && !PW),
-                  "scheme 2 tiles are 128 positions wide (experiment: 128 channels x 256 positions, 8 waves)");
+    static_assert(SCH != 2 || WN == 1 || C64, "scheme 2 tiles are 128 positions wide");
     using C = Cfg<KT, STRIDE, UPS, WM, WN, SCH, TBW, NCB>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifdef TQ_STAMP
@@ -157,15 +150,6 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
     const unsigned long long r_entry = __builtin_amdgcn_s_memrealtime();
 #endif
 
-#ifdef TQ_EXP_STAGGER
-    // experiment (round 5): the workgroups of one launch run in lock-step -- every CU in its load burst, then in its MFMA loop, then in
-    // its store burst (DESIGN_LOG.md).  Start them apart: workgroup i sleeps (hash(i) % 8) * p.exp_stagger * 64 cycles first, so that the
-    // bursts of one round spread over the round (first-round workgroups only matter: later ones start when a CU frees up).
-    if (p.exp_stagger > 0 && blockIdx.x < 256u * (64 * WM * WN == 512 ? 1u : 2u)) {
-        const unsigned k = (blockIdx.x * 2654435761u) >> 29;
-        for (unsigned i = 0; i < k * (unsigned)p.exp_stagger; ++i) __builtin_amdgcn_s_sleep(1);
-    }
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -347,11 +331,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
     float* gtab = reinterpret_cast<float*>(lds + (PW ? 4 * C::BUF : C::LDS_BYTES));   // [Cin] scale, [Cin] shift of sample b
     // bf16x3 small tile with the consumer-side GroupNorm fold (TqConvDesc.gn_fold): the fold runs behind the first chunk's loads and hands
     // that chunk's coefficients over through the table (see FOLD_LATE below); later chunks read what it wrote to global memory
-#ifdef TQ_ABL_FOLD_EARLY
-    constexpr bool FOLD_LATE0 = false;
-#else
     constexpr bool FOLD_LATE0 = SCH == 0 && TBW == 2 && ACT >= 1 && !PW && EPI == 0;
-#endif
     const bool fold0_pending = FOLD_LATE0 && p.cf_st0 != nullptr;
     auto chunk_base2 = [&](int stage, int& cs) -> const float* __attribute__((always_inline)) {
         const bool sk = FUSE && stage >= nchunks;
@@ -683,7 +663,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
     // Weight fragments live in two register buffers (taps alternate a, b, a, ...); after tap k its buffer is refilled with
     // tap k+2 of this chunk or, wrapping, with the next chunk's tap of the same parity, so every chunk starts with a = tap 0,
     // b = tap 1 already in flight.
-    Frag wa[C::NW], wb[NCB == 4 ? 1 : C::NW];   // (64-channel waves: ONE buffer, see mma_stream1)
+    Frag wa[C::NW], wb[C::NW];
 #ifndef TQ_LDS_DEPTH2
 #define TQ_LDS_DEPTH2 1
 #endif
@@ -694,7 +674,6 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
     // MFMAs that consume them, across tap boundaries too (a per-tap restart exposed the LDS latency KT times per chunk).
     auto mma_stream = [&](const unsigned char* hi_plane, const unsigned char* lo_plane, int s0, auto ntaps_c, auto first_tap_c)
         __attribute__((always_inline)) {
-        if constexpr (NCB == 2) {
         constexpr int NTAPS = decltype(ntaps_c)::value, K0 = decltype(first_tap_c)::value;
         constexpr int DEP = LDS_DEP, NB = LDS_DEP + 1, NS = NTAPS * TBW;
         Frag bf[NB][C::NBF];
@@ -717,60 +696,11 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        }
-    };
-
-    // 64-channel waves (NCB == 4): the KT x TBW steps of a chunk with the tap's sixteen weight fragments in ONE register buffer.  A
-    // block's four fragments are replaced by the next (chunk, tap) step's as soon as the tap's last t-block has issued that block's
-    // MFMAs; the wave then waits for them at the next tap's first step (hipcc's counted vmcnt) -- a stall of one L2 round trip per
-    // tap that the SIMD's other wave covers with its own MFMAs (the older wave of a SIMD wins MFMA issue, so the two alternate by
-    // themselves; a second buffer would be 64 more registers).  Activation fragments are read one step ahead.
-    auto mma_block2 = [&](const Frag (&w)[C::NW], const Frag (&f)[C::NBF], int tb, int cbk) __attribute__((always_inline)) {
-        const i32x8 bc = {(int)f[2].u.x, (int)f[2].u.y, (int)f[2].u.z, (int)f[2].u.w,
-                          (int)f[3].u.x, (int)f[3].u.y, (int)f[3].u.z, (int)f[3].u.w};
-        acc[cbk][tb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[cbk * 4 + 0].u), __builtin_bit_cast(f16x8, f[0].u), acc[cbk][tb], 0, 0, 0);
-        acc[cbk][tb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[cbk * 4 + 1].u), __builtin_bit_cast(f16x8, f[1].u), acc[cbk][tb], 0, 0, 0);
-        const Frag& c0 = w[cbk * 4 + 2];
-        const Frag& c1 = w[cbk * 4 + 3];
-        const i32x8 ac = {(int)c0.u.x, (int)c0.u.y, (int)c0.u.z, (int)c0.u.w, (int)c1.u.x, (int)c1.u.y, (int)c1.u.z, (int)c1.u.w};
-        acc[cbk][tb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ac, bc, acc[cbk][tb], 2, 2, 0, (int)c1.u.z, 0, (int)f[3].u.z);
-    };
-    auto mma_stream1 = [&](const unsigned char* hi_plane, const unsigned char* lo_plane, int s0) __attribute__((always_inline)) {
-        if constexpr (NCB == 4 && SCH == 2) {
-            constexpr int NS = KT * TBW;
-            Frag bf[2][C::NBF];
-            int b0 = tap_base(0), b0n = b0;
-            read_b(hi_plane, lo_plane, b0, 0, bf[0]);
-#pragma unroll
-            for (int st = 0; st < NS; ++st) {
-                const int kk = st / TBW, tb = st % TBW;
-                if (tb == 0 && kk + 1 < KT) b0n = tap_base(kk + 1);
-                if (st + 1 < NS) read_b(hi_plane, lo_plane, ((st + 1) / TBW) == kk ? b0 : b0n, (st + 1) % TBW, bf[(st + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (tb < TBW - 1) {
-                    mma_step(wa, bf[st & 1], tb);
-                } else {
-                    const int nx = s0 + kk + 1 < last_step ? s0 + kk + 1 : last_step;   // (the final refill re-reads the last fragments)
-                    const uint4* wp = wbase + (size_t)nx * wstep;
-#pragma unroll
-                    for (int cbk = 0; cbk < NCB; ++cbk) {
-                        mma_block2(wa, bf[st & 1], tb, cbk);
-#ifndef TQ_ABL_NCB4_NOREFILL   // (ablation, wrong numerics: the tap's weights are never replaced = a weight prefetch that costs nothing)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) wa[cbk * 4 + q].u = wp[(cbk * 4 + q) * 64];
-#endif
-                    }
-                    b0 = b0n;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
     };
 
     auto compute = [&](int chunk, int buf) __attribute__((always_inline)) {
         const unsigned char* hi_plane = lds + buf * C::BUF;
-        if constexpr (NCB == 4) mma_stream1(hi_plane, hi_plane + C::PLANE, chunk * KT);
-        else mma_stream(hi_plane, hi_plane + C::PLANE, chunk * KT, std::integral_constant<int, KT>{}, std::integral_constant<int, 0>{});
+        mma_stream(hi_plane, hi_plane + C::PLANE, chunk * KT, std::integral_constant<int, KT>{}, std::integral_constant<int, 0>{});
     };
 
     // skip stage j: one (centre) tap.  Buffer a holds this step's weights and b the next one's (the last main chunk's
@@ -791,11 +721,9 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
             mma_step(wa, bf[tb % NB], tb);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (NCB == 2) {
 #pragma unroll
-            for (int q = 0; q < C::NW; ++q) wa[q] = wb[q];
-            load_w(nchunks * KT + j + 2, wb);
-        }
+        for (int q = 0; q < C::NW; ++q) wa[q] = wb[q];
+        load_w(nchunks * KT + j + 2, wb);
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -810,25 +738,14 @@ __global__ __launch_bounds__(64 * WM * WN, ((TBW == 4 && NCB == 2 && SCH == 0) ?
     // from the source tensors' partial statistics here -- the arithmetic of tq_gn_finalize (gn_fold_sample: bit-identical coefficients for
     // any workgroup size) -- writes them where the prologue below (and, later, the backward) reads them, and goes on; every workgroup of
     // a sample writes the same bits.  Replaces the tq_gn_finalize launch in front of this one: a launch-bound plan (<= 4 samples: ~100
-    // dependent launches of 5-30 us) loses 45 % of its launches for ~3 us more in the prologue of each conv.
-#ifdef TQ_ABL_FOLD_EARLY   // (A/B build: the small tile of scheme 2 folds in front of its loads too, as until the end of round 6)
-    constexpr bool FOLD_EARLY = TBW == 2 && ACT >= 1 && !PW && EPI == 0;
-#else
-    constexpr bool FOLD_EARLY = TBW == 2 && SCH != 2 && ACT >= 1 && !PW && EPI == 0 && !FOLD_LATE0;   // (both schemes of the small tile fold behind their first loads, below)
-#endif
-    if constexpr (FOLD_EARLY) {
-        if (p.cf_st0) {   // (uniform over the launch)
-            gn_fold_sample<false, false>(reinterpret_cast<double*>(lds), b, p.cf_st0, p.C0, p.cf_st1, p.C1, p.T_in, p.cf_ns0, p.cf_ns1, p.cf_gamma,
-                                         p.cf_beta, const_cast<float*>(p.gscale), const_cast<float*>(p.gshift), p.cf_mean_rstd);
-            __syncthreads();   // the coefficients (global) are read back by other threads; the LDS scratch becomes the staging buffers
-        }
-    }
-    // ... and in the fp16 + MX-fp6 scheme (the small tile; the default tiles as an experiment, TQDNE_GN_FOLD=1): the fold runs AFTER the first
+    // dependent launches of 5-30 us) loses 45 % of its launches for ~3 us more in the prologue of each conv.  The bf16x3 small tile folds
+    // behind its first chunk's loads (FOLD_LATE0 above).
+    // In the fp16 + MX-fp6 scheme (the small tile; the default tiles as an experiment, TQDNE_GN_FOLD=1): the fold runs AFTER the first
     // chunk's staging loads and the first weight fragments have been requested (gtab_store below), so that its statistics loads share
     // their round trip, and leaves the coefficients in the LDS table directly -- what it adds to a workgroup is its arithmetic and three
     // barriers, not a global round trip (the small tile folded in FRONT of its loads until the end of round 6: two round trips in a row
     // in launches that are one dependent chain of latencies).
-    constexpr bool FOLD_LATE = SCH == 2 && ACT >= 1 && !PW && EPI == 0 && (TBW == 8 || TBW == 2) && !FOLD_EARLY;
+    constexpr bool FOLD_LATE = SCH == 2 && ACT >= 1 && !PW && EPI == 0 && (TBW == 8 || TBW == 2);
     const bool fold_late = FOLD_LATE && p.cf_st0 != nullptr;
     float4 gt_a = make_float4(0.f, 0.f, 0.f, 0.f), gt_s = gt_a;
     int gt_i = 0;
@@ -938,9 +855,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
         stage_load(0);
         if (wave_active) {
             load_w(0, wa);
-            if constexpr (NCB == 2) {
-                if (KT > 1 || nskip > 0) load_w(1, wb);
-            }
+            if (KT > 1 || nskip > 0) load_w(1, wb);
         }
         gtab_store();
         if constexpr (FOLD_LATE0) {
@@ -961,29 +876,6 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
             unsigned long long* tl = tq_timeline + blockIdx.x * 8;
             tl[0] = r_entry; tl[1] = __builtin_amdgcn_s_memrealtime(); tl[4] = t_entry; tl[5] = t_begin;
         }
-#endif
-#ifdef TQ_SKEW
-        // Half-phase skew of the two waves of a SIMD (8-wave tile: waves w and w + 4 share one): waves 4-7 convert + store their
-        // share of chunk c + 1 BEFORE their MFMA phase of chunk c (from loads issued one chunk earlier), waves 0-3 after theirs, so
-        // that one of the two is in its matrix stream while the other one stages.  Same barriers, same LDS hand-over: at the start
-        // of an iteration every wave has left the MFMA phase that read the buffer about to be overwritten.
-        // Diagnostic build only (-DTQ_SKEW): parity-green and spill-free in the fp6 layout (232-242 registers), but measured no
-        // faster (18-step sample 164.7 vs 165.7 ms, single layers 0-7 % slower): moving staging between the two waves of a SIMD
-        // is zero-sum here, as MI355X_MICROARCH.md's two-waves-per-SIMD section predicts.
-        if constexpr (!FUSE && SCH == 2 && WM == 8) {
-            // (ONE copy of the MFMA stream: two copies behind a wave-uniform branch made hipcc spill ~60 registers)
-            const bool skew = wave >= 4;
-            if (skew && nstages > 1) stage_load(1);
-            for (int c = 0; c + 1 < nstages; ++c) {
-                if (skew) stage_write(c + 1, (c + 1) & 1);
-                const int nxt = c + (skew ? 2 : 1);
-                stage_load(nxt < nstages ? nxt : nstages - 1);
-                if (wave_active) compute(c, c & 1);
-                if (!skew) stage_write(c + 1, (c + 1) & 1);
-                __syncthreads();
-            }
-            if (wave_active) compute(nstages - 1, (nstages - 1) & 1);
-        } else
 #endif
         if constexpr (!FUSE) {
             for (int c = 0; c + 1 < nstages; ++c) {
@@ -1143,7 +1035,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
     const int Cr = poly ? (p.C_out >> 1) : p.C_out;
     const int ph = (poly && co_wave >= Cr) ? 1 : 0;
     const int co_real = co_wave - ph * Cr;
-    // statistics slot = the 128 positions of a wave column (TBW == 8), of the workgroup (slim tile), or the workgroup's 32 positions
+    // statistics slot = the 128 positions of a wave column (TBW == 8), of the workgroup (64-position waves), or the workgroup's 32 positions
     // (small tile: the host sized the statistics tensor, p.nslots, for 32-position slots)
     const int slot = poly ? 2 * ((t0 >> 7) + wn) + ph : (TBW == 2 ? (t0 >> 5) : (t0 >> 7) + (TBW == 8 ? wn : 0));
     const float* emb_b = (p.flags & TQ_CONV_EMB) ? p.emb + (size_t)b * p.emb_stride : nullptr;
@@ -1174,11 +1066,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
     // store-complete + load round trips in a row per wave.
     const bool res_epi = (!RES_EARLY || poly) && (p.flags & TQ_CONV_RES);
     float4 rq[TBW][NCB];
-#ifdef TQ_ABL_EPI_SERIAL   // (A/B build: the loads inside the store loop, as in rounds 1-5)
-    if (false) {
-#else
     if (res_epi) {   // (wave-uniform)
-#endif
 #pragma unroll
         for (int tb = 0; tb < TBW; ++tb) {
             const int t = t0 + wn * C::WT + tb * 16 + (lane & 15);
@@ -1205,11 +1093,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
                 float4 v = make_float4(acc[cbk][tb][0] + add[cbk].x, acc[cbk][tb][1] + add[cbk].y,
                                        acc[cbk][tb][2] + add[cbk].z, acc[cbk][tb][3] + add[cbk].w);
                 if (res_epi) {
-#ifdef TQ_ABL_EPI_SERIAL
-                    const float4 r = *reinterpret_cast<const float4*>(p.res + o);
-#else
                     const float4 r = rq[tb][cbk];
-#endif
                     v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
                 }
 #ifdef TQ_ABL_NOEPI
@@ -1234,7 +1118,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
             }
         }
         if constexpr (TBW == 4) {
-            // slim tile: the two waves of a channel half cover the two 64-position halves of ONE 128-position statistics slot; the
+            // 64-position waves: the two waves of a channel half cover the two 64-position halves of ONE 128-position statistics slot; the
             // second one hands its sums over through LDS (the staging buffers are idle) and the first one stores the slot's total
             __syncthreads();
             float* red = reinterpret_cast<float*>(lds) + (wm * 4 + (lane >> 4)) * (8 * NCB);   // [wm][kq][cbk][j][2]
@@ -1257,58 +1141,14 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
             const int co = co_real + cbk * 16 + 4 * (lane >> 4);
             if ((lane & 15) == 0 && slot < p.nslots && (TBW == 8 || wn == 0)) {
                 float* st = p.stats + (((size_t)b * p.nslots + slot) * Cr + co) * 2;
-#ifdef TQ_BUILD_EXPERIMENTS
-                if (p.gf_counters) {
-                    // fused finalisation: the last-arriving workgroup of sample b reads these pairs in THIS launch -- 8-byte
-                    // agent-scope atomic stores (write-through, global_store_dwordx2 sc1), read back with the matching loads
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned long long u = (unsigned long long)__float_as_uint(s1[cbk][j]) |
-                                                     ((unsigned long long)__float_as_uint(s2[cbk][j]) << 32);
-                        __hip_atomic_store(reinterpret_cast<unsigned long long*>(st + 2 * j), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                } else
-#endif
-                {
-                    *reinterpret_cast<float4*>(st) = make_float4(s1[cbk][0], s2[cbk][0], s1[cbk][1], s2[cbk][1]);
-                    *reinterpret_cast<float4*>(st + 4) = make_float4(s1[cbk][2], s2[cbk][2], s1[cbk][3], s2[cbk][3]);
-                }
+                *reinterpret_cast<float4*>(st) = make_float4(s1[cbk][0], s2[cbk][0], s1[cbk][1], s2[cbk][1]);
+                *reinterpret_cast<float4*>(st + 4) = make_float4(s1[cbk][2], s2[cbk][2], s1[cbk][3], s2[cbk][3]);
                 // range guard: max|y| <= sqrt(sum of squares); (65504 / 2)^2 = 1.0727e9.  NaN / inf fail the comparison too
                 const float q = fmaxf(fmaxf(s2[cbk][0], s2[cbk][1]), fmaxf(s2[cbk][2], s2[cbk][3]));
                 if (p.range_flag && !(q < 1.0727e9f)) *p.range_flag = 1;
             }
         }
     }
-#ifdef TQ_BUILD_EXPERIMENTS
-    if constexpr (!PW) {
-        if (p.gf_counters) {   // (uniform over the launch; every wave of the workgroup is here: the host refuses ragged channel tiles)
-            // GroupNorm finalisation by the last arriver (TqGnFuse): every storing wave drains its stores, the workgroup meets, ONE
-            // lane takes the sample's ticket (agent-scope atomic add, returning); the workgroup whose ticket completes the sample
-            // -- tickets count up for ever: (ticket + 1) % workgroups-per-sample == 0 -- folds the statistics of that sample.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            int* flag = reinterpret_cast<int*>(lds);
-            if (tid == 0) {
-                const unsigned long long t = __hip_atomic_fetch_add(p.gf_counters + b, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *flag = ((t + 1ull) % (unsigned long long)p.gf_narrive) == 0ull ? 1 : 0;
-            }
-            __syncthreads();
-            const bool last = *flag != 0;
-            __syncthreads();   // (the flag word is part of the fold's scratch)
-            if (last) {
-                const int Cown = poly ? Cr : p.C_out;
-                const int ns = p.nslots;
-                double* sh = reinterpret_cast<double*>(lds);
-                if (p.gf_partner_first)
-                    gn_fold_sample<false, true>(sh, b, p.gf_partner, p.gf_Cp, p.stats, Cown, poly ? 2 * p.T_out : p.T_out, ns, ns, p.gf_gamma,
-                                                p.gf_beta, p.gf_gscale, p.gf_gshift, p.gf_mean_rstd);
-                else
-                    gn_fold_sample<true, false>(sh, b, p.stats, Cown, p.gf_partner, p.gf_Cp, poly ? 2 * p.T_out : p.T_out, ns, ns, p.gf_gamma,
-                                                p.gf_beta, p.gf_gscale, p.gf_gshift, p.gf_mean_rstd);
-            }
-        }
-    }
-#endif
     } else {
         // data gradient: acc = d loss / d xhat.  Chain through dropout, SiLU and the folded GroupNorm scale of the
         // FORWARD conv's prologue:  g = acc * mask/(1-p) * silu'(u), u = a*x + s  (the GN statistics' own dependence
@@ -1339,11 +1179,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
         const bool need_x = p.bflags & (TQ_BWD_GN | TQ_BWD_SILU | TQ_BWD_STATS);
         const bool accum = p.bflags & TQ_BWD_ACCUM;
         f32x4 lq[TBW][2];   // (a vector type like the accumulators: as HIP float4 structs the batch stayed in scratch memory)
-#ifdef TQ_ABL_EPI_SERIAL   // (A/B build: the loads inside the store loop, as in rounds 1-5)
-        if (false) {
-#else
         if (need_x || accum) {   // (wave-uniform)
-#endif
 #pragma unroll
             for (int tb = 0; tb < TBW; ++tb) {
                 const int t = t0 + wn * C::WT + tb * 16 + (lane & 15);
@@ -1368,11 +1204,7 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
                     if constexpr (SCH == 2) { v[0] *= dy_unscale; v[1] *= dy_unscale; v[2] *= dy_unscale; v[3] *= dy_unscale; }
                     float xv[4] = {0.f, 0.f, 0.f, 0.f};
                     if (need_x) {
-#ifdef TQ_ABL_EPI_SERIAL
-                        const f32x4 x4 = *reinterpret_cast<const f32x4*>(fx[cbk] + o);
-#else
                         const f32x4 x4 = lq[tb][cbk];
-#endif
                         xv[0] = x4[0]; xv[1] = x4[1]; xv[2] = x4[2]; xv[3] = x4[3];
                     }
                     if (p.bflags & TQ_BWD_SILU) {
@@ -1388,12 +1220,8 @@ next_pass:  // (PW only: a loop statement here costs the other instantiations re
                             v[j] = (drop_hash(dkey, e0 + j) >= p.drop_thresh) ? v[j] * p.drop_scale : 0.f;
                     }
                     if (accum) {
-#ifdef TQ_ABL_EPI_SERIAL
-                        f32x4 r = *reinterpret_cast<const f32x4*>(dst[cbk] + o);
-#else
                         f32x4 r = lq[tb][cbk];
                         if (need_x) r = *reinterpret_cast<const f32x4*>(dst[cbk] + o);
-#endif
                         v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
                     }
                     *reinterpret_cast<float4*>(dst[cbk] + o) = make_float4(v[0], v[1], v[2], v[3]);
@@ -1506,19 +1334,6 @@ int launch(const ConvArgs& a, hipStream_t stream) {
     const int n_ttiles = (a.T_out + C::NT - 1) / C::NT;
     const int n_ctiles = (a.C_out + C::MT - 1) / C::MT;
     const unsigned grid = (unsigned)(a.B * n_ttiles * (PW ? 1 : n_ctiles));
-#ifdef TQ_BUILD_EXPERIMENTS
-    if (a.gf_counters) {
-        // fused GroupNorm finalisation: every workgroup of a sample takes a ticket -- all its waves must reach the epilogue (no ragged
-        // channel tile) and the fold's scratch (2 C + 64 doubles) must fit the staging buffers it reuses
-        const int Ctot = ((a.flags & TQ_CONV_POLY2) ? a.C_out / 2 : a.C_out) + a.gf_Cp;
-        if (PW || EPI != 0 || (a.C_out % C::MT) || (size_t)(2 * Ctot + 64) * sizeof(double) > (size_t)LDS_BYTES) return TQ_ERR_SHAPE;
-        ConvArgs a2 = a;
-        a2.gf_narrive = n_ttiles * n_ctiles;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), LDS_BYTES, stream, a2);
-        TQ_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), LDS_BYTES, stream, a);
     TQ_CHECK_LAUNCH();
     return 0;
@@ -1547,10 +1362,7 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
     if (a.wfmt == TQ_WFMT_F16_MX6) {  // same shapes as TQ_WFMT_F16_MX8 (below), fp6 block-scaled corrections
         if constexpr (STRIDE == 1 && UPS == 0 && EPI == 1 && ACT == 0 && !FUSE) {   // data gradient (dy scaled by a power of two)
             if (a.C0 % 64 || a.C1) return TQ_ERR_SHAPE;
-            // TQDNE_DGRAD_TILE256=0 (A/B switch, round 6): 256-channel outputs as two co-resident 4-wave workgroups -- does a neighbour's
-            // MFMA stream cover the chain epilogue (x read back behind the last MFMA, +26 ... +73 % per launch)?
-            static const int dg256 = [] { const char* e = getenv("TQDNE_DGRAD_TILE256"); return (e && e[0] == '0') ? 0 : 1; }();
-            if (dg256 && a.C_out % 256 == 0) return launch<KT, STRIDE, UPS, 8, 1, EPI, ACT, FUSE, 2>(a, s);
+            if (a.C_out % 256 == 0) return launch<KT, STRIDE, UPS, 8, 1, EPI, ACT, FUSE, 2>(a, s);
             if (a.C_out % 128 == 0) return launch<KT, STRIDE, UPS, 4, 1, EPI, ACT, FUSE, 2>(a, s);
             if (a.C_out % 64 == 0) return launch<KT, STRIDE, UPS, 2, 2, EPI, ACT, FUSE, 2, false, 4>(a, s);   // (round 6: 64 / 192 input channels)
             return TQ_ERR_SHAPE;
@@ -1562,39 +1374,14 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
             }
             if constexpr (KT == 1 && UPS == 0 && ACT <= 1) {
                 const int cin = a.C0 + a.C1;
-                // TQ_CONV_CH_TILES (round 6; TQDNE_QKV_PW=0 / 1 forces one form everywhere: A/B switch): launch-bound plans take the
-                // channel-tiled form for the qkv projection too -- three times the workgroups of the input-stationary one
-                static const int force = [] { const char* e = getenv("TQDNE_QKV_PW"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-                const bool pw = force >= 0 ? force == 1 : !(a.flags & TQ_CONV_CH_TILES);
+                // TQ_CONV_CH_TILES (round 6): launch-bound plans take the channel-tiled form for the qkv projection too -- three times
+                // the workgroups of the input-stationary one
+                const bool pw = !(a.flags & TQ_CONV_CH_TILES);
                 if (pw && a.C_out % 256 == 0 && a.C_out >= 512 && (cin == 128 || cin == 256))
                     return launch<KT, STRIDE, UPS, 8, 1, EPI, ACT, FUSE, 2, true>(a, s);
             }
             // (256-channel outputs as two co-resident 4-wave workgroups instead of one 8-wave one: measured 2-8 % slower per layer)
-#ifdef TQ_EXP_NCB4
-            if constexpr (KT > 1 && UPS == 0 && EPI == 0 && !FUSE) {
-                // experiment (-DTQ_EXP_NCB4, TQDNE_CONV_NCB4=1): 4 x 2 waves of 64 channels x 64 positions instead of 8 x 1 of 32 x 128 --
-                // half the LDS reads per MFMA, ONE weight buffer.  Bit-identical convolution, 10-14 % SLOWER (87 -> 99 us, 256 -> 256,
-                // T = 1024): with one buffer a weight wait stands at every tap, and vmcnt retires in order, so the first of them also
-                // waits for the chunk's staging loads issued at the start of the phase (tools/experiments/ncb4_ab.py)
-                static const int ncb4 = [] { const char* e = getenv("TQDNE_CONV_NCB4"); return (e && e[0] == '1') ? 1 : 0; }();
-                if (ncb4 && a.C_out % 256 == 0 && !(a.flags & TQ_CONV_POLY2))
-                    return launch<KT, STRIDE, UPS, 4, 2, EPI, ACT, FUSE, 2, false, 4, 4>(a, s);
-            }
-#endif
-            // TQDNE_CONV_TILE256=0 (A/B switch, round 5): 256-channel outputs as two co-resident 4-wave workgroups (128 channels each) instead
-            // of one 8-wave one.  Per layer 2-8 % slower (round 2: co-resident workgroups of ONE launch run in lock-step, and every input
-            // tile is staged twice); re-measured under the 4-lane sampler, where co-resident workgroups of different lanes are out of phase
-            static const int tile256 = [] { const char* e = getenv("TQDNE_CONV_TILE256"); return (e && e[0] == '0') ? 0 : 1; }();
-            if (tile256 && a.C_out % 256 == 0) return launch<KT, STRIDE, UPS, 8, 1, EPI, ACT, FUSE, 2>(a, s);
-#ifdef TQ_EXP_WN2
-            if constexpr (KT == 5 && UPS == 0 && EPI == 0 && ACT >= 2) {
-                // experiment: 128 channels x 256 positions in ONE 8-wave workgroup instead of two co-resident 4-wave ones -- the weights
-                // (C_in x 128 x 5 x 2.2 B per tile: 540 KB for 384 -> 128) are streamed from L2 once per 256 positions instead of 128
-                static const int wn2 = [] { const char* e = getenv("TQDNE_CONV_WN2"); return (e && e[0] == '1') ? 1 : 0; }();
-                if (wn2 && a.C_out % 128 == 0 && !(a.flags & TQ_CONV_POLY2) && a.T_out % 256 == 0)
-                    return launch<KT, STRIDE, UPS, 4, 2, EPI, ACT, FUSE, 2>(a, s);
-            }
-#endif
+            if (a.C_out % 256 == 0) return launch<KT, STRIDE, UPS, 8, 1, EPI, ACT, FUSE, 2>(a, s);
             if (a.C_out % 128 == 0) return launch<KT, STRIDE, UPS, 4, 1, EPI, ACT, FUSE, 2>(a, s);
             if constexpr (KT == 5 && UPS == 0 && EPI == 0 && ACT >= 2) {   // round 6: the 64-channel ResBlock convs (with or without the fused skip conv)
                 if (a.C_out % 64 == 0 && !(a.flags & TQ_CONV_POLY2)) return launch<KT, STRIDE, UPS, 2, 2, EPI, ACT, FUSE, 2, false, 4>(a, s);
@@ -1627,19 +1414,6 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
     }
     if (a.C_out % 128 == 0) return launch<KT, STRIDE, UPS, 4, 1, EPI, ACT, FUSE>(a, s);
     if constexpr (STRIDE == 1) {
-#ifdef TQ_BUILD_EXPERIMENTS
-        if constexpr (UPS == 0 && EPI == 0 && KT == 5 && ACT != 3) {   // (the dropout prologue spills in this tile: training keeps 64 x 256)
-            // 64-channel outputs at T = 4096 are bound by their load / store bursts, not by MFMA cycles (section 5 of DESIGN.md).
-            // The slim tile (64 channels x 128 positions, 32 accumulator registers per wave, 152-168 registers) lets three
-            // workgroups share a CU instead of two.  Measured (tools/slim_ab.py, B = 64, same box, bit-identical outputs): SLOWER --
-            // 64 -> 64: 52-55 vs 50 us, 64+64 -> 64: 90 vs 82, 128+64 -> 64: 118-123 vs 115: 2048 tiles on 768 slots are 2.7 rounds
-            // where 1024 tiles on 512 slots are exactly 2, and every tile re-streams the weights and 4 halo rows for half the
-            // positions.  Off by default; TQDNE_CONV_SLIM=1 selects it.
-            static const int slim = [] { const char* e = getenv("TQDNE_CONV_SLIM"); return (e && e[0] == '1') ? 1 : 0; }();
-            if (slim && a.C_out % 64 == 0 && !(a.flags & TQ_CONV_POLY2))
-                return launch<KT, STRIDE, UPS, 2, 2, EPI, ACT, FUSE, 0, false, 4>(a, s);
-        }
-#endif
         if (a.C_out % 64 == 0) return launch<KT, STRIDE, UPS, 2, 2, EPI, ACT, FUSE>(a, s);
         return launch<KT, STRIDE, UPS, 1, 2, EPI, ACT, FUSE>(a, s);
     } else {

@@ -2,7 +2,6 @@
 // (conv1d_kernel.hpp) is instantiated in conv1d_fwd_k5a/k5b/k13.hip, conv1d_resample.hip and conv1d_dgrad.hip; this file validates
 // the descriptors, fills ConvArgs and hands over to those translation units' entry points (conv_args.hpp).
 #include <cmath>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "conv_args.hpp"
@@ -15,11 +14,6 @@ extern "C" int tq_conv_tile_co(int C_out) {
     if (C_out % 128 == 0) return 128;
     if (C_out % 64 == 0) return 64;
     return 32;
-}
-
-static int conv_exp_stagger() {   // (TQDNE_CONV_STAGGER: see -DTQ_EXP_STAGGER in conv1d_kernel.hpp; 0 in default builds' kernels: unread)
-    static const int v = [] { const char* e = getenv("TQDNE_CONV_STAGGER"); return e ? atoi(e) : 0; }();
-    return v;
 }
 
 static int conv1d_fwd_impl(const TqConvDesc* d, const float* x0, const float* x1, const float* gscale, const float* gshift,
@@ -90,7 +84,7 @@ static int conv1d_fwd_impl(const TqConvDesc* d, const float* x0, const float* x1
     if (d->t_tile) {   // the small tile: see TqConvDesc.t_tile for what it is built for (the dispatcher refuses the rest)
         const int need = TQ_CONV_GN | TQ_CONV_SILU;
         if (d->t_tile != 32) return TQ_ERR_ARG;
-        if (d->ktaps != 5 || d->stride != 1 || d->upsample || kv_planes || (d->flags & need) != need || (d->flags & TQ_CONV_POLY2) || d->gn_fuse)
+        if (d->ktaps != 5 || d->stride != 1 || d->upsample || kv_planes || (d->flags & need) != need || (d->flags & TQ_CONV_POLY2))
             return TQ_ERR_SHAPE;
         a.t_tile = 32;
         a.nslots = (d->T_out + 31) / 32;
@@ -115,13 +109,11 @@ static int conv1d_fwd_impl(const TqConvDesc* d, const float* x0, const float* x1
     a.kv = kv_planes; a.kvH = kvH; a.kvD = kvD; a.kvTp = kvTp; a.kvscale = kvscale; a.kv_vf16 = (kv_planes && kv_vf16) ? 1 : 0;
     a.range_flag = d->range_flag;
     a.in_amax = nullptr;
-    a.gf_counters = nullptr; a.exp_stagger = conv_exp_stagger(); a.gf_partner = nullptr; a.gf_Cp = 0; a.gf_partner_first = 0; a.gf_narrive = 0;
-    a.gf_gamma = a.gf_beta = nullptr; a.gf_gscale = a.gf_gshift = a.gf_mean_rstd = nullptr;
     a.cf_st0 = a.cf_st1 = a.cf_gamma = a.cf_beta = nullptr; a.cf_mean_rstd = nullptr; a.cf_ns0 = a.cf_ns1 = 0;
     if (d->gn_fold) {   // consumer-side GroupNorm fold (ABI 7): this launch forms its own folded coefficients (see TqGnFold)
         const TqGnFold* f = d->gn_fold;
         // built for the small tile, and (experiment) for the default tiles of the fp16 + MX-fp6 scheme -- the dispatcher refuses the rest
-        if (!(d->flags & TQ_CONV_GN) || kv_planes || d->gn_fuse || (a.t_tile != 32 && d->wfmt != TQ_WFMT_F16_MX6)) return TQ_ERR_SHAPE;
+        if (!(d->flags & TQ_CONV_GN) || kv_planes || (a.t_tile != 32 && d->wfmt != TQ_WFMT_F16_MX6)) return TQ_ERR_SHAPE;
         if (!f->stats0 || !f->gamma || !f->beta || (d->C_in1 > 0 && !f->stats1)) return TQ_ERR_ARG;
         const int s0 = f->slot0 ? f->slot0 : STAT_SLOT, s1 = f->slot1 ? f->slot1 : STAT_SLOT;
         if ((s0 != STAT_SLOT && s0 != 32) || (s1 != STAT_SLOT && s1 != 32)) return TQ_ERR_ARG;
@@ -130,19 +122,7 @@ static int conv1d_fwd_impl(const TqConvDesc* d, const float* x0, const float* x1
         a.cf_ns0 = (d->T_in + s0 - 1) / s0; a.cf_ns1 = (d->T_in + s1 - 1) / s1;
         a.cf_gamma = f->gamma; a.cf_beta = f->beta; a.cf_mean_rstd = f->mean_rstd;
     }
-#ifndef TQ_BUILD_EXPERIMENTS
-    if (d->gn_fuse) return TQ_ERR_ARG;   // reserved: the in-launch GroupNorm fold is an experiment (TQDNE_BUILD_EXPERIMENTS=1 builds it)
-#else
-    if (d->gn_fuse) {
-        const TqGnFuse* g = d->gn_fuse;
-        if (!(d->flags & TQ_CONV_STATS) || kv_planes || !g->counters || !g->gamma || !g->beta || !g->gscale || !g->gshift) return TQ_ERR_ARG;
-        if (g->C_partner < 0 || (g->C_partner > 0 && !g->partner_stats)) return TQ_ERR_ARG;
-        const int Cown = (d->flags & TQ_CONV_POLY2) ? d->C_out / 2 : d->C_out;
-        if ((Cown + g->C_partner) % GN_GROUPS) return TQ_ERR_SHAPE;
-        a.gf_counters = g->counters; a.gf_partner = g->partner_stats; a.gf_Cp = g->C_partner; a.gf_partner_first = g->partner_first;
-        a.gf_gamma = g->gamma; a.gf_beta = g->beta; a.gf_gscale = g->gscale; a.gf_gshift = g->gshift; a.gf_mean_rstd = g->mean_rstd;
-    }
-#endif
+    if (d->reserved1) return TQ_ERR_ARG;   // reserved pointer
 
     if (d->stride == 2 || d->upsample) {
         if (a.flags & (TQ_CONV_GN | TQ_CONV_SILU | TQ_CONV_DROPOUT)) return TQ_ERR_SHAPE;  // resampling convs take raw inputs
@@ -151,12 +131,6 @@ static int conv1d_fwd_impl(const TqConvDesc* d, const float* x0, const float* x1
     if (a.kv) {  // qkv projection with the pre-split K / V epilogue: k = 1, plain or folded-GN prologue
         return conv_launch_qkv(a, stream);
     }
-#ifdef TQ_BUILD_EXPERIMENTS
-    {   // the one-wave-per-SIMD kernel where it is built (conv1d_w4.hip); TQ_ERR_SHAPE = "not mine", nothing launched
-        const int rc = conv1d_w4_launch(a, d->ktaps, stream);
-        if (rc != TQ_ERR_SHAPE) return rc;
-    }
-#endif
     switch (d->ktaps) {
         case 1: return conv_launch_fwd_k1(a, stream);
         case 3: return conv_launch_fwd_k3(a, stream);
@@ -212,8 +186,6 @@ extern "C" int tq_conv1d_bwd_data(const TqConvBwdDesc* d, const float* dy, const
     }
     a.kv = nullptr; a.kvH = a.kvD = a.kvTp = 0; a.kvscale = 1.f; a.kv_vf16 = 0;
     a.range_flag = nullptr;
-    a.gf_counters = nullptr; a.exp_stagger = conv_exp_stagger(); a.gf_partner = nullptr; a.gf_Cp = 0; a.gf_partner_first = 0; a.gf_narrive = 0;
-    a.gf_gamma = a.gf_beta = nullptr; a.gf_gscale = a.gf_gshift = a.gf_mean_rstd = nullptr;
     a.cf_st0 = a.cf_st1 = a.cf_gamma = a.cf_beta = nullptr; a.cf_mean_rstd = nullptr; a.cf_ns0 = a.cf_ns1 = 0;
     return conv_launch_dgrad(a, d->ktaps, stream);
 }

@@ -1,5 +1,4 @@
-// Launch arguments of the fused 1-D convolution kernels (conv1d_mfma.hip: two waves per SIMD; conv1d_w4.hip: one wave per SIMD)
-// and the fp6 block-scale helpers both use.
+// Launch arguments of the fused 1-D convolution kernels (conv1d_kernel.hpp) and the fp6 block-scale helpers.
 #pragma once
 #include "common.hpp"
 #include "../../include/tqdne_hip.h"
@@ -45,15 +44,6 @@ struct ConvArgs {
     int* range_flag;  // see TqConvDesc.range_flag
     int t_tile;       // 0: the default tiles (128 / 256 positions per workgroup); 32: the small tile (TqConvDesc.t_tile)
     const uint32_t* in_amax;  // data gradient, TQ_WFMT_F16_MX6: bit pattern of max|dy| over the whole tensor (see TqConvBwdDesc.dy_amax)
-    // fused GroupNorm finalisation (TqConvDesc.gn_fuse): the workgroup that completes a sample's statistics folds them
-    unsigned long long* gf_counters;   // nullptr: off
-    const float* gf_partner;
-    int gf_Cp, gf_partner_first, gf_narrive;
-    const float* gf_gamma;
-    const float* gf_beta;
-    float* gf_gscale;
-    float* gf_gshift;
-    float* gf_mean_rstd;
     // consumer-side GroupNorm fold (TqConvDesc.gn_fold): statistics of the two sources, slots per source, affine parameters; cf_st0 == nullptr: off
     const float* cf_st0;
     const float* cf_st1;
@@ -61,7 +51,6 @@ struct ConvArgs {
     const float* cf_gamma;
     const float* cf_beta;
     float* cf_mean_rstd;
-    int exp_stagger;   // experiment builds (-DTQ_EXP_STAGGER): s_sleep units by which the workgroups of a launch start apart; else 0, unread
 };
 
 
@@ -100,10 +89,5 @@ inline bool conv_wide_table(const ConvArgs& a) { return a.C0 + a.C1 > CONV_GTAB_
 int conv_launch_fwd_wide(const ConvArgs& a, int ktaps, int act, bool fuse, hipStream_t stream);
 int conv_launch_fwd_wide_k5(const ConvArgs& a, int act, bool fuse, hipStream_t stream);
 int conv_launch_fwd_wide_k13(const ConvArgs& a, int ktaps, int act, hipStream_t stream);
-
-// conv1d_w4.hip (TQDNE_BUILD_EXPERIMENTS builds only): the one-wave-per-SIMD variant of the stride-1 forward launches in the fp16 +
-// MX-fp6 scheme.  Returns TQ_ERR_SHAPE (nothing launched) for a launch it is not built for; the caller then takes the
-// two-waves-per-SIMD kernel.
-int conv1d_w4_launch(const ConvArgs& a, int ktaps, hipStream_t stream);
 
 }  // namespace tq

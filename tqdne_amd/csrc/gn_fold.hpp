@@ -1,15 +1,15 @@
 // GroupNorm32 statistics -> folded per-(b, c) scale / shift of ONE sample, by the threads of one workgroup.
-// Shared by gn_finalize_kernel (small_ops.hip: one workgroup per sample, its own launch) and the fused form in the conv epilogue
-// (conv1d_mfma.hip: the workgroup that completes a sample's statistics folds them, "last arriver") so that both produce
-// bit-identical coefficients: same per-thread summation order, same fp64 combine.
+// Shared by gn_finalize_kernel (small_ops.hip: one workgroup per sample, its own launch) and the consumer-side fold in the conv prologue
+// (conv1d_kernel.hpp, TqConvDesc.gn_fold) so that both produce bit-identical coefficients: same per-thread summation order, same fp64
+// combine.
 #pragma once
 #include "common.hpp"
 
 namespace tq {
 
-// One {sum, sum of squares} pair of the partial statistics.  COHERENT = true: the pair may have been written by another workgroup
-// of THIS launch (as one 8-byte agent-scope atomic store, behind that workgroup's drain + barrier + arrival ticket): read it with
-// an 8-byte agent-scope atomic load (global_load_dwordx2 sc1: served by L2 / memory, never by this CU's L1) -- the "8-byte agent
+// One {sum, sum of squares} pair of the partial statistics.  COHERENT = true (no caller today: every fold reads statistics that
+// earlier launches wrote): the pair may have been written by another workgroup of THIS launch (as one 8-byte agent-scope atomic
+// store, behind that workgroup's drain + barrier + arrival ticket): read it with an 8-byte agent-scope atomic load (global_load_dwordx2 sc1: served by L2 / memory, never by this CU's L1) -- the "8-byte agent
 // atomics on both sides" form of cdna_hip_programming.md, Guideline 16.
 template <bool COHERENT>
 __device__ __forceinline__ float2 gn_load_pair(const float* p) {
@@ -73,11 +73,7 @@ __device__ __forceinline__ void gn_fold_sample(double* sh, int b, const float* _
 #pragma unroll
             for (int u = 0; u < 8; ++u) { s1 += (double)v[u].x; s2 += (double)v[u].y; }
         }
-#ifdef TQ_ABL_FOLD_REMAINDER   // (A/B build: the remainder batch always issued, as in rounds 3-5)
-        if (true) {
-#else
         if (s < nslots) {
-#endif
             // up to 7 left: again all loads first (clamped index, masked add).  (Round 6: skipped when nothing is left -- the
             // clamped loads of an empty remainder were one more dependent global round trip in every fold.)
             float2 v[7];

@@ -9,13 +9,7 @@
 using namespace tq;
 
 extern "C" int tq_abi_version(void) { return TQ_ABI_VERSION; }
-extern "C" int tq_build_flags(void) {
-#ifdef TQ_BUILD_EXPERIMENTS
-    return TQ_BUILD_EXPERIMENTS_BIT;
-#else
-    return 0;
-#endif
-}
+extern "C" int tq_build_flags(void) { return 0; }   // (no optional parts; kept for ABI 5 callers)
 
 // =================================================================================================
 // GroupNorm32 finalisation: per-channel partial (sum, sumsq) of up to two concatenated sources ->
@@ -428,9 +422,7 @@ extern "C" int tq_head_conv_fwd(const float* x, const float* gscale, const float
     if (c_out && (!c_skip || !skip_src)) return TQ_ERR_ARG;
     const size_t sh = head_conv_lds(C_in, C_out, ktaps);
     if (B <= 0 || T <= 0 || sh == 0) return TQ_ERR_SHAPE;
-    // TQDNE_HEAD_FWD=lds: the round-3 kernel for every shape (A/B switch)
-    static const int row_form = [] { const char* e = getenv("TQDNE_HEAD_FWD"); return (e && e[0] == 'l') ? 0 : 1; }();
-    if (row_form && (C_out <= 4 || C_out == 6 || C_out == 8 || C_out == 16) && (C_in == 16 || C_in == 32 || C_in == 64 || C_in == 128)) {
+    if ((C_out <= 4 || C_out == 6 || C_out == 8 || C_out == 16) && (C_in == 16 || C_in == 32 || C_in == 64 || C_in == 128)) {
         const int nt = (T + (64 - (ktaps - 1)) - 1) / (64 - (ktaps - 1));
         const int per = C_out <= 8 ? C_out : 8;   // output channels per launch (16 = two launches of 8: the input tile is staged twice)
         const size_t st_ = (size_t)64 * (C_in + 4), sp_ = (size_t)4 * ktaps * per * 68;

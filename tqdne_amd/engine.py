@@ -53,43 +53,30 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
 class Act:
     """A channels-last activation (B, T, C) and, optionally, its per-channel partial statistics."""
 
-    __slots__ = ("buf", "stats", "C", "T", "grad", "gw", "prod", "slot")
+    __slots__ = ("buf", "stats", "C", "T", "grad", "gw", "slot")
 
     def __init__(self, buf, stats, C, T, slot=STAT_SLOT):
         self.buf, self.stats, self.C, self.T = buf, stats, C, T
         self.slot = slot   # positions per statistics slot (32 for the output of a small-tile conv, TqConvDesc.t_tile)
-        self.prod = None   # descriptors (TqConvDesc) of the launches that write this tensor and its statistics, if they can fold them
         self.grad = None   # gradient buffer (training plans only)
         self.gw = False    # backward-plan construction: has some op already written the gradient?
 
 
-FUSE_SKIP = os.environ.get("TQDNE_FUSE_SKIP", "1") != "0"  # A/B switch for the fused skip-conv launch
-# GroupNorm finalisation inside the launch that completes the statistics (TqConvDesc.gn_fuse, "last arriver") instead of a
-# tq_gn_finalize launch per GroupNorm: TQDNE_GN_FUSE=1.  Built, parity- and concurrency-tested (tests/test_concurrency.py), and
-# measured NEUTRAL (18-step sample at B = 64, 4 lanes: 165.7 vs 166.0 ms; 1 lane 174.5 vs 172.8; tiny UNet B = 4: 41.9 vs 41.6 ms):
-# what the 49 launches cost comes back as the fold's dependent-load chain on the tail of the producing launch -> off by default
-# (an experiment since round 4: only libraries built with TQDNE_BUILD_EXPERIMENTS=1 carry it)
-GN_FUSE = os.environ.get("TQDNE_GN_FUSE", "0") == "1"
-# Round 6: the TRAINING forward of Upsample runs in the two-phase k = 3 form too (it was the inference form only), and its gradients are
-# those of that k = 3 conv (engine_bwd._bwd_up_poly): 3/5 of the multiply-adds in all three passes, no (B, 2T, C) scratch gradient, no
-# tq_pair_sum.  TQDNE_POLYPHASE_TRAIN=0: the k = 5 launches over the upsampled gather, as before.
-POLY_TRAIN = os.environ.get("TQDNE_POLYPHASE_TRAIN", "1") != "0"
 FUSE_SKIP_CO = 32  # smallest output-channel multiple fused (measured: 128 -> +3.9 %, 64 -> +1.3 % more on the bench step)
 # Small position tile (TqConvDesc.t_tile = 32) for the ResBlock convs of launch-bound plans: a plan whose batch is at most SMALL_TILE_B
 # samples launches 16-64 workgroups of the default tiles per conv on 256 compute units (tiny UNet, B = 4: 12-30 us per conv launch).
 # The choice is a property of the PLAN (its batch), never of how many lanes run: lanes of a larger batch have >= 8 samples each, so
 # the lane-versus-one-lane bit-identity holds.  A sample computed in a small batch differs from the same sample in a large one at
-# rounding level only through the association order of the GroupNorm statistics.  TQDNE_SMALL_TILE=0 turns it off.
-SMALL_TILE_B = int(os.environ.get("TQDNE_SMALL_TILE_B", "4")) if os.environ.get("TQDNE_SMALL_TILE", "1") != "0" else 0
+# rounding level only through the association order of the GroupNorm statistics.
+SMALL_TILE_B = 4
 # ... and, per LAYER of a plan that has the device to itself (UNetEngine.solo: not a lane of a multi-lane sampler), where the default
 # tile's grid B * ceil(T_out / 128) is at most SMALL_TILE_WGS workgroups -- the T = 512 level of a 16-sample plan: 64 workgroups on 256
 # compute units, 36 -> 26 us per 256 -> 256 conv, cfg3's sample 92.5 -> 87.0 ms.  Lanes keep the default tile: four lanes fill the
 # device between them, and there the small tile's 4x weight traffic costs 161 -> 180 ms per B = 64 sample; the mid level (128
 # workgroups) loses 7-18 % alone (profiles/r04_v_small_tile_per_layer.txt).
-SMALL_TILE_WGS = int(os.environ.get("TQDNE_SMALL_TILE_WGS", "64")) if os.environ.get("TQDNE_SMALL_TILE", "1") != "0" else 0
+SMALL_TILE_WGS = 64
 # Round 6: a small-tile conv folds its own GroupNorm (TqConvDesc.gn_fold, consumer side) instead of a tq_gn_finalize launch in front of it:
-# a plan of <= 4 samples is ~100 dependent launches of 5-30 us, and 45 % of them were these.  TQDNE_GN_FOLD_SMALL=0: the launches.
-GN_FOLD_SMALL = os.environ.get("TQDNE_GN_FOLD_SMALL", "1") != "0"
+# a plan of <= 4 samples is ~100 dependent launches of 5-30 us, and 45 % of them were these.
 # ... and (experiment) the default tiles of the fp16 + MX-fp6 scheme, with the fold behind the first chunk's loads: TQDNE_GN_FOLD=1
 GN_FOLD_DEFAULT = os.environ.get("TQDNE_GN_FOLD", "0") == "1"
 CONCURRENT_LANE0 = 8   # plan-cache lane ids from here on: sub-batch plans that run concurrently (see UNetModel._engine)
@@ -121,15 +108,6 @@ def side_stream(dev, i: int = 1) -> "torch.cuda.Stream":
     return s
 
 
-def hiprio_stream(dev) -> "torch.cuda.Stream":
-    """a high-priority stream of the device (experiment TQDNE_BWD_HIPRIO, engine_bwd.BackwardPlan.run)"""
-    key = (str(dev), "hiprio")
-    s = _SIDE_STREAMS.get(key)
-    if s is None:
-        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev, priority=-1)
-    return s
-
-
 def reserve_side_streams(dev, n: int = 3):
     """Create the pool's first ``n`` streams NOW (called when the first plan of a device is built).  Stream creation order decides
     how ROCm spreads streams over hardware queues: with the three lane streams created AFTER anything had captured a HIP graph
@@ -158,7 +136,6 @@ def reserve_side_streams(dev, n: int = 3):
 
 
 _PACK_TABLES: dict = {}
-PACK_BATCH = os.environ.get("TQDNE_PACK_BATCH", "1") != "0"   # A/B switch: 0 = one launch per tensor (rounds 1-2 behaviour)
 
 
 def pack_batch(lib, dev, jobs, stream, capturing=False):
@@ -171,7 +148,7 @@ def pack_batch(lib, dev, jobs, stream, capturing=False):
     ent = _PACK_TABLES.get(key)
     # (tables are never evicted: a launch queued on another stream may still read one, and the caching allocator would hand its
     # block to the next allocation; they are ~40 bytes per job, and past 4096 distinct lists new ones run as per-tensor launches)
-    if ent is None and (capturing or not PACK_BATCH or len(jobs) < 2 or len(_PACK_TABLES) >= 4096):
+    if ent is None and (capturing or len(jobs) < 2 or len(_PACK_TABLES) >= 4096):
         ent = False
     if ent is None:
         arr = (_lib.TqPackJob * len(jobs))()
@@ -230,8 +207,6 @@ class PackedStore:
 
 
 def get_store(model, device) -> PackedStore:
-    if os.environ.get("TQDNE_SHARED_STORE", "1") == "0":   # A/B switch: a private store per plan (the round-1 behaviour)
-        return PackedStore(device)
     stores = model.__dict__.setdefault("_packed_stores", {})
     st = stores.get(str(device))
     if st is None:
@@ -358,9 +333,6 @@ class UNetEngine:
         self.poly_sites: List[Tuple[ConvSite, ConvSite]] = []   # (derived two-phase k = 3 site, the Upsample conv it restates)
         self.dropout_descs: List[TqConvDesc] = []
         self.acts: List[Act] = []
-        self.gn_bufs: List[torch.Tensor] = []   # every GroupNorm's folded coefficients (see poison_gn)
-        self.gn_fused = 0                         # GroupNorms folded inside their producer's launch
-        self.poison_gn = False               # tests set it on the plan object (tests/test_concurrency.py); no environment switch
         self._probe = None
         self.tape = []
         self.last_rec = None
@@ -424,32 +396,13 @@ class UNetEngine:
         self.op_bytes.append(nbytes)
 
     def _gn(self, srcs: Sequence[Act], norm: torch.nn.GroupNorm, defer: bool = False):
-        """Folded scale / shift (B, C) of a GroupNorm over the (concatenated) sources.  Where the most recent source is written by a
-        conv launch that can do it, the fold rides in that launch (TqGnFuse: the workgroup completing a sample's statistics folds
-        them); otherwise -- the stem's output, a tensor that is already the last source of another GroupNorm -- a tq_gn_finalize
-        launch.  The coefficient buffers are registered in ``gn_bufs`` so that tests can poison them (``poison_gn``): a fold that
-        did not happen then surfaces as NaN instead of as the previous evaluation's (nearly right) coefficients."""
+        """Folded scale / shift (B, C) of a GroupNorm over the (concatenated) sources: a tq_gn_finalize launch, or (``defer``) the
+        consuming conv's own prologue where that conv folds (see ``_conv``)."""
         C_ = sum(s.C for s in srcs)
         gscale, gshift = self._empty(self.B, C_), self._empty(self.B, C_)
         mean_rstd = self._empty(self.B, 32, 2)
-        self.gn_bufs += [gscale, gshift, mean_rstd]
         s0 = srcs[0]
         s1 = srcs[1] if len(srcs) > 1 else None
-        prod = s0.prod if GN_FUSE else None
-        if GN_FUSE and not _lib.has_experiments():
-            raise RuntimeError("TQDNE_GN_FUSE=1 needs the experiments build of the library (TQDNE_BUILD_EXPERIMENTS=1)")
-        if prod and all(not d.gn_fuse for d in prod):
-            for d in prod:   # (one TqGnFuse and one ticket counter per launch form: the forms tile the tensor differently)
-                f = _lib.TqGnFuse()
-                counters = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
-                self._keep += [f, counters]
-                f.counters = counters.data_ptr()
-                f.partner_stats, f.C_partner, f.partner_first = (_p(s1.stats), s1.C, 0) if s1 is not None else (None, 0, 0)
-                f.gamma, f.beta = _p(norm.weight), _p(norm.bias)
-                f.gscale, f.gshift, f.mean_rstd = _p(gscale), _p(gshift), _p(mean_rstd)
-                d.gn_fuse = C.pointer(f)
-            self.gn_fused += 1
-            return gscale, gshift, mean_rstd
         fin = ((self.lib.tq_gn_finalize, (
             _p(s0.stats), s0.C, _p(s1.stats) if s1 else None, s1.C if s1 else 0, self.B, s0.T,
             _p(norm.weight), _p(norm.bias), _p(gscale), _p(gshift), _p(mean_rstd), s0.slot, s1.slot if s1 else 0), "gn_finalize", 0),
@@ -483,10 +436,10 @@ class UNetEngine:
         srcs_c = [s0.C, (s1.C if s1 else 0)] + ([a.C for a in skip[0]] if skip is not None else [])
         k5_act = site.K == 5 and gn is not None and silu and stride == 1 and not upsample and qkv_planes is None
         _check_width_limits(site.name, site.C_in, site.C_out)
-        wfmt = _lib.forward_wfmt(site.C_out, srcs_c, stride, upsample, fused_skip=skip is not None, k5_act=k5_act, gn=gn is not None) if launch else 0
+        wfmt = _lib.forward_wfmt(site.C_out, srcs_c, stride, upsample, k5_act=k5_act, gn=gn is not None) if launch else 0
         # the small tile where it is built (see SMALL_TILE_B): the ResBlock convs of a small-batch plan
         small = (launch and (self.B <= SMALL_TILE_B or (self.solo and self.B * ((T_out + 127) // 128) <= SMALL_TILE_WGS)) and k5_act
-                 and wfmt in (_lib.TQ_WFMT_BF16X3, _lib.TQ_WFMT_F16_MX6) and not GN_FUSE)
+                 and wfmt in (_lib.TQ_WFMT_BF16X3, _lib.TQ_WFMT_F16_MX6))
         if small and wfmt == _lib.TQ_WFMT_F16_MX6 and site.C_out % 128:
             wfmt = _lib.TQ_WFMT_BF16X3   # (the small tile's fp16 + MX-fp6 form is the 128-channel one)
         if launch and ckpt_tag is not None and self.ckpt:
@@ -506,14 +459,14 @@ class UNetEngine:
             fold_fits = site.C_in <= fold_max
             fold_default = (GN_FOLD_DEFAULT and not small and k5_act and wfmt == _lib.TQ_WFMT_F16_MX6 and self.scheme == "auto"
                             and getattr(self.m, "_conv_scheme", "auto") == "auto" and fold_fits)
-            if fold_default and launch and not self.ckpt and not GN_FUSE:
+            if fold_default and launch and not self.ckpt:
                 # the tq_gn_finalize launch stays in the plan as a no-op: the range-guard fallback moves this conv to the three-product
                 # scheme, whose default tiles do not fold -- it then gets its launch back (_set_scheme_bf16x3)
                 fn, fargs, fname, ffl = pend["fin"][0]
                 self._fold_default_ops = getattr(self, "_fold_default_ops", [])
                 self._fold_default_ops.append((len(self.ops), fn, d))
                 self._emit((_noop_launch, fargs, fname + " (folded into its consumer)", ffl), nbytes=0)
-            if launch and ((small and GN_FOLD_SMALL and fold_fits) or fold_default) and not self.ckpt and not GN_FUSE:
+            if launch and ((small and fold_fits) or fold_default) and not self.ckpt:
                 f = _lib.TqGnFold()
                 ps0, ps1 = pend["srcs"]
                 f.stats0, f.stats1 = _p(ps0.stats), (_p(ps1.stats) if ps1 is not None else None)
@@ -582,9 +535,8 @@ class UNetEngine:
             # (two-phase form: its 2 * ceil(T_in / 128) statistics slots must be the tensor's ceil(2 T_in / 128))
             if (upsample and site.K == 5 and (T_in % STAT_SLOT == 0 or T_in % STAT_SLOT > STAT_SLOT // 2) and site.C_out % 32 == 0 and gn is None and res is None
                     and emb_ptr is None and os.environ.get("TQDNE_POLYPHASE_UPSAMPLE", "1") != "0"):
-                self._poly_desc = None
                 infer_op = self._polyphase_op(site, d, s0, s1, out, flops)
-                if POLY_TRAIN and s1 is None:
+                if s1 is None:
                     op = infer_op   # (one form for both kinds of forward; the backward plan differentiates that form)
             if qkv_planes is not None:  # (ws, H, D): K / V straight into the attention kernel's pre-split planes
                 ws, H_, D_ = qkv_planes
@@ -595,14 +547,8 @@ class UNetEngine:
                     _p(out.buf), _p(ws), H_, D_, self.kv_v_format), "conv:" + site.name + "+split", flops)
                 self._vfmt_ops.append(len(self.ops_infer))
             self._emit(op, infer_op, nbytes=nbytes)
-            if stats and qkv_planes is None:   # (its inference form, the two-phase up-sampling conv, is a launch of its own shape)
-                poly = getattr(self, "_poly_desc", None)
-                out.prod = [d] + ([poly] if (infer_op is not None and poly is not None) else [])
-                self._poly_desc = None
-        if launch and skip is not None and stats:
-            out.prod = [d]
         self.last_rec = ConvRec(site, d, list(srcs), gn, out, stride, upsample, silu, dropout_site is not None)
-        if launch and upsample and POLY_TRAIN and s1 is None and self.poly_sites and self.poly_sites[-1][1] is site:
+        if launch and upsample and s1 is None and self.poly_sites and self.poly_sites[-1][1] is site:
             self.last_rec.poly = (self.poly_sites[-1][0], self._last_poly_desc)
         return out
 
@@ -627,7 +573,6 @@ class UNetEngine:
         if d2.flags & TQ_CONV_STATS:
             d2.range_flag = self.range_flag.data_ptr()
         self._keep.append(d2)
-        self._poly_desc = d2
         self._last_poly_desc = d2
         return (self.lib.tq_conv1d_fwd, (
             C.byref(d2), _p(s0.buf), _p(s1.buf) if s1 else None, None, None, _p(ps.packed), _p(site.bias), None, None,
@@ -730,7 +675,7 @@ class UNetEngine:
             assert len(srcs) == 1
             out = self._conv([h1], self._site(name + ".out_layers.3", conv2), gn=g2, silu=True, res=srcs[0],
                              dropout_site=self._site_counter)
-        elif FUSE_SKIP and conv2.weight.shape[2] == 5 and conv2.weight.shape[0] % FUSE_SKIP_CO == 0 and all(a.C % 32 == 0 for a in srcs):
+        elif conv2.weight.shape[2] == 5 and conv2.weight.shape[0] % FUSE_SKIP_CO == 0 and all(a.C % 32 == 0 for a in srcs):
             # the 1x1 skip conv rides in conv2's launch (extra K chunks); it is still recorded for its gradients
             site2, site_sk = self._site_pair(name + ".out_layers.3", conv2, name + ".skip_connection", rb.skip_connection)
             self._conv(srcs, site_sk, stats=False, launch=False)
@@ -808,16 +753,6 @@ class UNetEngine:
         idx = max((i for i, op in enumerate(self.ops) if op[2].startswith(name_prefix)), key=lambda i: self.ops[i][3])
         self._probe = Probe(idx, self.ops[idx][2], self.ops[idx][3])
         return self._probe
-
-    def _poison(self):
-        """test mode (``plan.poison_gn = True``): NaN into every GroupNorm coefficient buffer before a forward, so that a
-        fold that is skipped, raced or mis-addressed is a loud NaN in the output instead of the previous call's coefficients"""
-        if self.poison_gn and not torch.cuda.is_current_stream_capturing():
-            for t in self.gn_bufs:
-                t.fill_(float("nan"))
-            for a in self.acts:   # (the partial statistics too: a fold that ran before its sample was complete reads NaN)
-                if a.stats is not None:
-                    a.stats.fill_(float("nan"))
 
     # ------------------------------------------------------------------ range guard of the fp16-range scheme
     def _set_scheme_bf16x3(self):
@@ -1028,7 +963,6 @@ class UNetEngine:
             ncond = cond.shape[1]
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         self._range_poll(True)
-        self._poison()
         self.repack(stream)
         p = float(m.dropout) if train else 0.0
         for d in self.dropout_descs:
@@ -1177,7 +1111,6 @@ class SeqEngine(UNetEngine):
             raise ValueError(f"plan was built for {(B, m.in_channels, T)}, got {tuple(x.shape)}")
         x = x.contiguous()
         stream = torch.cuda.current_stream(self.dev).cuda_stream
-        self._poison()
         self.repack(stream)
         p = float(getattr(m, "dropout", 0.0)) if train else 0.0
         for d in self.dropout_descs:

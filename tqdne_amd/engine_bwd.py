@@ -33,23 +33,13 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-# Column sums of dy (bias / time-embedding gradients) inside the weight-gradient launch (tq_conv1d_bwd_weight_colsum) instead of a pass
-# of their own: built and parity-tested, but measured SLOWER on the paper UNet (train step 32.1 vs 31.0 ms, same box): the LDS
-# adds and the extra barrier cost the k = 5 kernel more than the 1.9 ms of tq_colsum launches they replace.  Default off.
-FUSE_COLSUM = __import__("os").environ.get("TQDNE_FUSE_COLSUM", "0") != "0"
-
-
 # Weight-gradient launches on a second HIP stream next to the rest of the sweep (see BackwardPlan.run): measured -0.9 ms on the
 # 27 ms training step of the paper UNet at B = 64 (same box, twice).  TQDNE_BWD_STREAMS=1: everything on one stream.
 BWD_STREAMS = int(__import__("os").environ.get("TQDNE_BWD_STREAMS", "2"))
-BWD_HIPRIO = __import__("os").environ.get("TQDNE_BWD_HIPRIO", "0") == "1"
 
 # Round 4.  (1) Column sums (and max|.|) of a gradient tensor inside the tq_gn_bwd_apply launch that writes it last, instead of a
-# tq_colsum pass of their own (TQDNE_FUSE_APPLY_COLSUM=0: separate passes).  (2) Data gradients in the fp16 + MX-fp6 scheme on dy
-# scaled by a power of two taken from that max (TqConvBwdDesc.wfmt / dy_amax), where the shape allows (64 | C_dy, 128 | C_dx);
-# TQDNE_DGRAD_SCHEME=bf16x3 keeps round 3's three-product scheme everywhere.
-FUSE_APPLY_COLSUM = __import__("os").environ.get("TQDNE_FUSE_APPLY_COLSUM", "1") != "0"
-DGRAD_SCHEME = __import__("os").environ.get("TQDNE_DGRAD_SCHEME", "f16mx6").lower()
+# tq_colsum pass of their own.  (2) Data gradients in the fp16 + MX-fp6 scheme on dy scaled by a power of two taken from that max
+# (TqConvBwdDesc.wfmt / dy_amax), where the shape allows (64 | C_dy, 128 | C_dx).
 DGRAD_MX6_C64 = __import__("os").environ.get("TQDNE_DGRAD_MX6_C64", "0") == "1"   # (off by default: see _lib.MX6_C64)
 N_AMAX = 160   # blocks for max|dy| (one per gradient tensor that feeds a data gradient), kept in the tail of the flat buffer
 
@@ -229,9 +219,10 @@ class BackwardPlan:
 
     # ------------------------------------------------------------------ emitters
     def _wgrad(self, rec, dy, bias_colsum=True, colsum=None):
-        """weight gradient of one conv; the column sums of dy that the block needs anyway (bias gradients, the per-sample gradient of
-        the broadcast time embedding) ride in the same launch: ``colsum`` = (per-sample destination address | None, its row stride,
-        bias gradient tensor | None, second bias gradient tensor | None); ``bias_colsum``: default = this conv's own bias."""
+        """weight gradient of one conv, behind the column sums of dy that the block needs anyway (bias gradients, the per-sample
+        gradient of the broadcast time embedding; ``_colsum_pass``): ``colsum`` = (per-sample destination address | None, its row
+        stride, bias gradient tensor | None, second bias gradient tensor | None); ``bias_colsum``: default = this conv's own bias.
+        (The sums inside the weight-gradient launch, tq_conv1d_bwd_weight_colsum's optional arguments, measured slower: not used.)"""
         lib, site = self.lib, rec.site
         need = lib.tq_conv1d_bwd_weight_workspace(C.byref(rec.desc))
         self.ws_bytes = max(getattr(self, "ws_bytes", 0), need)
@@ -240,17 +231,13 @@ class BackwardPlan:
         s1 = rec.srcs[1] if len(rec.srcs) > 1 else None
         if colsum is None and bias_colsum and site.bias is not None:
             colsum = (None, 0, site.bias, None)
-        bc, stride, c1, c2 = colsum if colsum is not None else (None, 0, None, None)
-        if FUSE_COLSUM is False and colsum is not None:   # A/B switch: the column sums as their own pass over dy
-            self._colsum_pass(dy, rec.out.T if rec.out is not None else rec.desc.T_out, site.C_out, bc, stride, c1, c2, site.name)
-            bc, stride, c1, c2 = None, 0, None, None
+        if colsum is not None:
+            self._colsum_pass(dy, rec.out.T if rec.out is not None else rec.desc.T_out, site.C_out, *colsum, site.name)
             self._wgrad_ops[-1] = len(self.ops)
         self.op_flops[len(self.ops)] = 2 * site.C_in * site.C_out * site.K * rec.desc.T_out * self.B
         self.ops.append([lib.tq_conv1d_bwd_weight_colsum, [C.byref(rec.desc), _p(dy), _p(s0.buf), _p(s1.buf) if s1 else None,
                                                            _p(rec.gn[0]) if rec.gn else None, _p(rec.gn[1]) if rec.gn else None,
-                                                           _p(self.g(site.weight)), None, 0, bc, stride,
-                                                           _p(self.g(c1)) if c1 is not None else None,
-                                                           _p(self.g(c2)) if c2 is not None else None], "wgrad:" + site.name])
+                                                           _p(self.g(site.weight)), None, 0, None, 0, None, None], "wgrad:" + site.name])
 
     def _colsum_pass(self, dy, T_dy, C_dy, bc, stride, c1, c2, name):
         """column sums (bias / per-sample embedding gradients) and max|dy| of the gradient tensor ``dy`` (B, T_dy, C_dy): inside the
@@ -258,7 +245,7 @@ class BackwardPlan:
         lib = self.lib
         amax = self.amax_ptr(dy.data_ptr())
         wr = self._grad_writer.get(dy.data_ptr())
-        if FUSE_APPLY_COLSUM and wr is not None and wr[0][0] is lib.tq_gn_bwd_apply:
+        if wr is not None and wr[0][0] is lib.tq_gn_bwd_apply:
             # the launch that writes dy last is a tq_gn_bwd_apply: it forms the sums from its registers (its op is rewritten in
             # place; the gradients are final no earlier than before, so g() still records the current position)
             op = wr[0]
@@ -285,7 +272,7 @@ class BackwardPlan:
         # (no width limit in either scheme: a data gradient has no GroupNorm prologue, hence no coefficient table -- C_dy = 3072 of a wide
         # qkv projection and C_dx = 1024 + 1024 of a wide output block run the same tiles)
         cin_ok = site.C_in % 128 == 0 or (site.C_in % 64 == 0 and DGRAD_MX6_C64)
-        mx6 = (DGRAD_SCHEME == "f16mx6" and _lib.requested_scheme() == "f16mx6"
+        mx6 = (_lib.requested_scheme() == "f16mx6"
                and amax is not None and site.C_out % 64 == 0 and cin_ok
                and getattr(self.e, "scheme", "auto") == "auto" and getattr(self.m, "_conv_scheme", "auto") == "auto")
         want = 5 if mx6 else 1
@@ -510,7 +497,7 @@ class BackwardPlan:
         x.gw = True
 
     def _bwd_up_poly(self, t):
-        """Upsample whose training forward ran in the two-phase k = 3 form (engine.POLY_TRAIN): the gradients of THAT conv, with the
+        """Upsample whose training forward ran in the two-phase k = 3 form (every such forward a backward may follow): the gradients of THAT conv, with the
         output gradient (B, 2T, C) read as (B, T, 2C) -- row m of the view = [row 2m | row 2m + 1] = the two phases' channel blocks.
           bias:    column sums of d out over the real (B, 2T, C) view (+ its max|.| for the fp16-range data gradient)
           weights: k = 3 weight gradient d W2 (2C, C_in, 3), folded onto the five taps (tq_upsample_poly_wgrad_fold)
@@ -582,25 +569,9 @@ class BackwardPlan:
             dx.mul_(last["in_scale"][:, None, None])
         return dx
 
-    def run(self, *args, **kw):
-        """The reverse sweep (``_run``).  TQDNE_BWD_HIPRIO=1 (experiment, round 6): the sweep's chain -- data gradients, GroupNorm backward,
-        column sums -- runs on a HIGH-priority stream while the weight gradients stay on the normal-priority side stream, so that the
-        chain's small launches are dispatched ahead of the weight gradients' pending workgroups instead of queueing behind them (under
-        rocprofv3 a `gn_bwd_finalize` launch takes 33-43 us next to a weight gradient and 8 us alone)."""
-        if BWD_HIPRIO and self._trace is None and BWD_STREAMS == 2 and not torch.cuda.is_current_stream_capturing():
-            from .engine import hiprio_stream
-            main_t = torch.cuda.current_stream(self.dev)
-            hp = hiprio_stream(self.dev)
-            hp.wait_stream(main_t)
-            with torch.cuda.stream(hp):
-                res = self._run(*args, **kw)
-            main_t.wait_stream(hp)
-            return res
-        return self._run(*args, **kw)
-
-    def _run(self, dpred: torch.Tensor, gloss: torch.Tensor, clone: bool = True, on_bucket=None, bucket_elems: int = 4 << 20,
+    def run(self, dpred: torch.Tensor, gloss: torch.Tensor, clone: bool = True, on_bucket=None, bucket_elems: int = 4 << 20,
              tail_fill=None, want_dx: bool = False):
-        """``want_dx``: also form d loss / d x of the forward's input; left in ``self.last_dx`` (B, C_in, T).
+        """The reverse sweep.  ``want_dx``: also form d loss / d x of the forward's input; left in ``self.last_dx`` (B, C_in, T).
         ``on_bucket(flat_slice)``: called from inside the sweep, right after the launch that finalises the last gradient of
         each bucket of >= ``bucket_elems`` floats has been enqueued (buckets = contiguous slices of the flat buffer in the
         order the sweep completes them; every rank cuts them identically).  The data-parallel trainer starts the slice's
@@ -779,7 +750,7 @@ class BackwardPlan:
         # B x E / 32^2 = 16 output tiles: as one job that is 16 workgroups walking 176 dependent load -> barrier -> FMA rounds
         # (measured 160 us for 0.18 GFLOP).  Split along the reduction into KS partial products (same launch as the weight /
         # bias gradients), summed and multiplied by SiLU'(emb) by a one-row "GEMM" with a vector of ones in a launch of its own.
-        KS = max(1, min(int(__import__("os").environ.get("TQDNE_EMB_KSPLIT", "16")), Et // 256, B))   # (env: A/B switch, 1 = one job)
+        KS = max(1, min(16, Et // 256, B))
         self.d_emb_part = self._empty(KS, B, E)
         kcut = [(Et * i // KS) // 32 * 32 for i in range(KS)] + [Et]
         lv1 = [job(_p(demb), 1, Et, _p(e.silu_emb), E, 1, _p(self.g_emb_w), E, Et, E, B),          # d W_proj
