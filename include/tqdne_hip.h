@@ -376,7 +376,8 @@ int tq_attention_bwd_ws(const float* qkv, const float* out, const float* dout, c
 int tq_attention_bwd_ws_kv(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                            void* workspace, const void* kv_planes, int B, int T, int H, int D, hipStream_t stream);
 
-/* ABI 8.  Every head size D with 8 | D and 8 <= D <= 256 (attention_hd.hip): the first-generation kernels on the smallest tile in
+/* ABI 8.  Every head size D with 8 | D and 8 <= D <= 256 (attention_hd.hip): the first-generation kernels (attention_g1.hpp, the text that tq_attention_fwd / tq_attention_bwd instantiate for
+ * an exact head size, here instantiated with the padding masks) on the smallest tile in
  * {32, 64, 128, 256} that holds the head; channels >= D are zero-filled on load and skipped on store, strides and the D^-1/4 scale are
  * those of the true D.  Same tensors and layouts as tq_attention_fwd / tq_attention_bwd.  The entry points above keep their contract
  * (D in {32, 64, 128}, TQ_ERR_SHAPE otherwise).

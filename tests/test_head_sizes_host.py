@@ -76,11 +76,12 @@ def test_new_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
         name, meta = m.group(1), m.group(2)
         assert int(re.search(r"private_segment_fixed_size (\d+)", meta).group(1)) == 0, name   # no spills at all
         static_lds[name] = int(re.search(r"group_segment_fixed_size (\d+)", meta).group(1))
-    passes = {0: "attention_hd_kernel", 1: "attention_bwd_dq_hd_kernel", 2: "attention_bwd_dkv_hd_kernel"}
+    # (the PAD = true instantiations of the shared first-generation kernels, csrc/attention_g1.hpp)
+    passes = {0: "attention_kernel", 1: "attention_bwd_dq_kernel", 2: "attention_bwd_dkv_kernel"}
     seen = 0
     for tile in (32, 64, 128, 256):
         for p, stem in passes.items():
-            names = [n for n in static_lds if re.search(rf"\d+{stem}ILi{tile}E", n)]
+            names = [n for n in static_lds if re.search(rf"\d+{stem}ILi{tile}ELb1EE", n)]
             assert len(names) == 1, (tile, stem, sorted(static_lds))
             dyn = lib.tq_attention_hd_lds_bytes(tile, p)
             assert 0 < dyn and static_lds[names[0]] + dyn <= LDS_LIMIT, (names[0], static_lds[names[0]], dyn)

@@ -5,8 +5,16 @@
 Every kernel of OLD must be in NEW with identical machine code (the encoded instruction words, which are position independent) and
 identical .vgpr_count / .sgpr_count / .agpr_count / .group_segment_fixed_size / .private_segment_fixed_size / spill counts.  Names are
 compared demangled; a template argument list of NEW may carry extra trailing arguments (a new defaulted template parameter).  Kernels
-only in NEW are listed.  Needs no GPU; exit status 1 on any difference."""
+only in NEW are listed.  Needs no GPU; exit status 1 on any difference.
 
+    --rename OLD_REGEX=NEW_TEMPLATE   (repeatable) a kernel of OLD whose demangled name matches OLD_REGEX is paired with the kernel of NEW
+                                      named re.sub(OLD_REGEX, NEW_TEMPLATE, name): for kernels that were renamed or whose parameter list changed
+
+A pair whose instruction words differ gets a second look at the disassembly: "scalar argument loads only" if it is equal line for line
+once the immediate offset of the s_load_* instructions is masked (a kernel argument moved), else "same mnemonics apart from s_load / s_waitcnt"
+if the sequence of mnemonics is equal once those two kinds of line are dropped (scalar loads regrouped, registers renumbered)."""
+
+import collections
 import hashlib
 import os
 import re
@@ -54,7 +62,7 @@ def code_objects(so, tmp):
 
 
 def kernels(so, tmp):
-    """{demangled kernel name: (sha1 of the instruction words, metadata dict)}"""
+    """{demangled kernel name: (sha1 of the instruction words, metadata dict, instruction text lines)}"""
     res = {}
     for co in code_objects(so, tmp):
         notes = run(os.path.join(LLVM, "llvm-readelf"), "--notes", co).decode()
@@ -65,20 +73,22 @@ def kernels(so, tmp):
             meta[name] = {k: re.search(re.escape(k) + r":\s+(\S+)", blk).group(1) for k in META if re.search(re.escape(k) + r":\s+(\S+)", blk)}
         dis = run(os.path.join(LLVM, "llvm-objdump"), "-d", co).decode()
         cur, h = None, None
-        streams = {}
+        streams, text = {}, {}
         for line in dis.splitlines():
             m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
             if m:
                 cur = m.group(1)
                 streams[cur] = hashlib.sha1()
+                text[cur] = []
                 continue
             m = re.search(r"//\s*[0-9A-Fa-f]+:\s*((?:[0-9A-Fa-f]{8}\s*)+)(?:<.*>)?\s*$", line)
             if cur and m:
                 streams[cur].update(m.group(1).encode())
+                text[cur].append(" ".join(line.split("//")[0].split()))
         names = list(meta)
         dem = demangle(names)
         for mangled, d in zip(names, dem):
-            res[d] = (streams[mangled].hexdigest() if mangled in streams else None, meta[mangled])
+            res[d] = (streams[mangled].hexdigest() if mangled in streams else None, meta[mangled], text.get(mangled, []))
     return res
 
 
@@ -96,10 +106,31 @@ def strip_added_args(new_name, old_names):
     return None
 
 
-def main(old_so, new_so):
+def code_verdict(a, b):
+    """what is left of a difference in the instruction words, from the two disassemblies"""
+    def masked(t):
+        return [re.sub(r"(0x[0-9a-f]+|\d+)$", "#", l) if l.startswith("s_load_") else l for l in t]
+
+    def mnemonics(t):
+        return [l.split()[0] for l in t if not l.startswith(("s_load_", "s_waitcnt"))]
+    if masked(a) == masked(b):
+        return "scalar argument loads only"
+    if mnemonics(a) == mnemonics(b):
+        return "same mnemonics apart from s_load / s_waitcnt (%d / %d instructions)" % (len(a), len(b))
+    ca, cb = collections.Counter(mnemonics(a)), collections.Counter(mnemonics(b))
+    return "CODE differs (%d / %d instructions; counts of other mnemonics that changed: %s)" % (
+        len(a), len(b), {m: cb[m] - ca[m] for m in sorted(set(ca) | set(cb)) if ca[m] != cb[m]} or "none, order only")
+
+
+def main(old_so, new_so, renames=()):
     with tempfile.TemporaryDirectory() as tmp:
         old, new = kernels(old_so, tmp), kernels(new_so, tmp)
     alias = {}
+    for o in old:
+        for rx, tpl in renames:
+            n = re.sub(rx, tpl, o)
+            if n != o and o not in new and n in new:
+                alias.setdefault(o, []).append(n)
     for n in new:
         if n not in old:
             o = strip_added_args(n, old)
@@ -107,7 +138,7 @@ def main(old_so, new_so):
                 alias.setdefault(o, []).append(n)
     bad = 0
     counterpart = {}
-    for name, (h, meta) in sorted(old.items()):
+    for name, (h, meta, txt) in sorted(old.items()):
         # (several instantiations of NEW may extend one OLD name -- the default of the added parameter and other values of it: the one
         # that reproduces OLD is its counterpart)
         cands = [name] if name in new else alias.get(name, [])
@@ -115,18 +146,18 @@ def main(old_so, new_so):
             print("MISSING in new:", name)
             bad += 1
             continue
-        nn = next((c for c in cands if new[c] == (h, meta)), cands[0])
+        nn = next((c for c in cands if new[c][:2] == (h, meta)), cands[0])
         counterpart[name] = nn
-        h2, meta2 = new[nn]
+        h2, meta2, txt2 = new[nn]
         if h != h2 or h is None:
-            print("CODE differs:", name)
+            print("%s: %s -> %s" % (code_verdict(txt, txt2), name, nn))
             bad += 1
         if meta != meta2:
             print("METADATA differs:", name, {k: (meta.get(k), meta2.get(k)) for k in META if meta.get(k) != meta2.get(k)})
             bad += 1
     matched = set(counterpart.values())
     extra = sorted(n for n in new if n not in matched)
-    print("%d kernels in old, %d in new, %d renamed by added template arguments, %d only in new, %d differences"
+    print("%d kernels in old, %d in new, %d renamed, %d only in new, %d differences"
           % (len(old), len(new), sum(1 for k, v in counterpart.items() if k != v), len(extra), bad))
     for n in extra:
         m = new[n][1]
@@ -136,4 +167,9 @@ def main(old_so, new_so):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    argv, renames = sys.argv[1:], []
+    while "--rename" in argv:
+        i = argv.index("--rename")
+        renames.append(tuple(argv[i + 1].split("=", 1)))
+        del argv[i:i + 2]
+    sys.exit(main(argv[0], argv[1], renames))

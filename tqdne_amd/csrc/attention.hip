@@ -1,288 +1,9 @@
-// 1-D self-attention core of the tqdne UNet (QKVAttention, tqdne/blocks.py:156-190) for gfx950.
+// Attention entry points of the paper model's head sizes (32 / 64 / 128) for gfx950, and the second-generation kernels.
 //
-//   qkv (B, T, 3*H*D) channels-last, channel order [q heads | k heads | v heads]
-//   out[b, t, h*D + c] = sum_s softmax_s( (q*D^-1/4) . (k*D^-1/4) )[t, s] * v[s, c]
-//
-// Flash-style: the (T x T) score matrix of the reference (4 MB per sample per block at T=512) never
-// exists in HBM.  One workgroup = 64 queries of one (b, head), 4 waves x 16 queries; keys/values are
-// streamed in tiles of 64 through LDS; QK^T and PV run on v_mfma_f32_16x16x32_bf16 with the same
-// bf16 hi/lo 3-product split as the convolutions (scores feed an exponential, so single bf16 is not
-// accurate enough for the 1e-3 parity target); the online softmax is fp32, as in the reference.
-#include "common.hpp"
-#include "../../include/tqdne_hip.h"
-
-using namespace tq;
-
-namespace {
-
-constexpr int QT = 64;   // queries per workgroup
-constexpr int KTILE = 64;  // keys per tile
-
-// Round 6: ``ksplit`` > 1 -- the key tiles of one (b, head, query tile) are dealt over ``ksplit`` workgroups, each leaving its
-// un-normalised output rows, running maxima and row sums in ``part``; attn_combine_kernel merges them.  For grids far below the chip
-// (the tiny config's middle block at B = 4: one head of 128 channels, 32 workgroups walking 8 key tiles each).
-template <int D>
-__global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                           float* __restrict__ lse, int T, int H, float scale, int ksplit,
-                                                           float* __restrict__ part) {
-    constexpr int KS = D / 32;       // k-steps over the head dimension
-    constexpr int CB = D / 16;       // output column blocks
-    constexpr int KROW = D * 2 + 16;   // bytes per key row of the K image (padded)
-    constexpr int VROW = KTILE * 2 + 16;  // bytes per channel row of the V^T image
-    constexpr int PROW = KTILE * 2 + 16;  // bytes per query row of the P image
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    unsigned char* k_hi = lds;
-    unsigned char* k_lo = k_hi + KTILE * KROW;
-    unsigned char* v_hi = k_lo + KTILE * KROW;
-    unsigned char* v_lo = v_hi + D * VROW;
-    unsigned char* p_base = v_lo + D * VROW;  // [4 waves][2 planes][16][PROW]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nqt = (T + QT - 1) / QT;
-    const int grp = nqt * ksplit;
-    int bid = xcd_group_id(blockIdx.x, grp, gridDim.x / grp);  // the tiles of one (b, h) share an XCD's L2
-    const int ksid = bid % ksplit; bid /= ksplit;
-    const int qt = bid % nqt; bid /= nqt;
-    const int h = bid % H;
-    const int b = bid / H;
-    const int C3 = 3 * H * D;
-    const float* base = qkv + (size_t)b * T * C3;
-    const int q0 = qt * QT + wave * 16;
-    unsigned char* p_hi = p_base + wave * 2 * 16 * PROW;
-    unsigned char* p_lo = p_hi + 16 * PROW;
-
-    // ---- Q fragments (A operand: row = query l&15, k = d) kept in registers for the whole kernel
-    Frag qh[KS], ql[KS];
-    {
-        const int q = q0 + (lane & 15);
-        const bool ok = q < T;
-        const float* qp = base + (size_t)(ok ? q : 0) * C3 + h * D + 8 * (lane >> 4);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            float4 a = make_float4(0, 0, 0, 0), c = a;
-            if (ok) {
-                a = *reinterpret_cast<const float4*>(qp + ks * 32);
-                c = *reinterpret_cast<const float4*>(qp + ks * 32 + 4);
-            }
-            const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                __bf16 hh, ll;
-                split_bf16(v[j] * scale, hh, ll);
-                qh[ks].v[j] = hh; ql[ks].v[j] = ll;
-            }
-        }
-    }
-
-    f32x4 o[CB];
-#pragma unroll
-    for (int i = 0; i < CB; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[4], l_run[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m_run[r] = -INFINITY; l_run[r] = 0.f; }
-
-    const int nkt = (T + KTILE - 1) / KTILE;
-    const int kt_begin = ksid * nkt / ksplit, kt_end = (ksid + 1) * nkt / ksplit;   // (ksplit <= nkt: never empty)
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int s0 = kt * KTILE;
-        __syncthreads();  // previous tile fully consumed
-        // ---- stage K tile: thread -> (key = i / (D/4), 4 channels)
-        for (int i = tid; i < KTILE * (D / 4); i += 256) {
-            const int key = i / (D / 4), c4 = i % (D / 4);
-            float4 v = make_float4(0, 0, 0, 0);
-            if (s0 + key < T) v = *reinterpret_cast<const float4*>(base + (size_t)(s0 + key) * C3 + (H + h) * D + 4 * c4);
-            const float u[4] = {v.x * scale, v.y * scale, v.z * scale, v.w * scale};
-            bf16x4 hv, lv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { __bf16 hh, ll; split_bf16(u[j], hh, ll); hv[j] = hh; lv[j] = ll; }
-            *reinterpret_cast<bf16x4*>(k_hi + key * KROW + c4 * 8) = hv;
-            *reinterpret_cast<bf16x4*>(k_lo + key * KROW + c4 * 8) = lv;
-        }
-        // ---- stage V^T tile: thread -> (4 channels c4, 4 keys kg), transposed in registers
-        for (int i = tid; i < (KTILE / 4) * (D / 4); i += 256) {
-            const int c4 = i % (D / 4), kg = i / (D / 4);
-            float4 v[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int key = s0 + 4 * kg + kk;
-                v[kk] = make_float4(0, 0, 0, 0);
-                if (key < T) v[kk] = *reinterpret_cast<const float4*>(base + (size_t)key * C3 + (2 * H + h) * D + 4 * c4);
-            }
-            const float cols[4][4] = {{v[0].x, v[1].x, v[2].x, v[3].x}, {v[0].y, v[1].y, v[2].y, v[3].y},
-                                      {v[0].z, v[1].z, v[2].z, v[3].z}, {v[0].w, v[1].w, v[2].w, v[3].w}};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                bf16x4 hv, lv;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) { __bf16 hh, ll; split_bf16(cols[j][kk], hh, ll); hv[kk] = hh; lv[kk] = ll; }
-                *reinterpret_cast<bf16x4*>(v_hi + (4 * c4 + j) * VROW + kg * 8) = hv;
-                *reinterpret_cast<bf16x4*>(v_lo + (4 * c4 + j) * VROW + kg * 8) = lv;
-            }
-        }
-        __syncthreads();
-
-        // ---- S = Q K^T  (16 queries x 64 keys per wave)
-        f32x4 s[4];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            s[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int key = cb * 16 + (lane & 15);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                Frag bh, bl;
-                const int off = key * KROW + (ks * 4 + (lane >> 4)) * 16;
-                bh.u = *reinterpret_cast<const uint4*>(k_hi + off);
-                bl.u = *reinterpret_cast<const uint4*>(k_lo + off);
-                s[cb] = mfma_x3(qh[ks].v, ql[ks].v, bh.v, bl.v, s[cb]);
-            }
-        }
-        // ---- online softmax; lane holds rows 4*(lane>>4)+r, column cb*16 + (lane&15)
-        float alpha[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const bool valid = (s0 + cb * 16 + (lane & 15)) < T;
-                if (!valid) s[cb][r] = -INFINITY;
-                mx = fmaxf(mx, s[cb][r]);
-            }
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            const float m_new = fmaxf(m_run[r], mx);
-            alpha[r] = (m_run[r] == -INFINITY) ? 0.f : __expf(m_run[r] - m_new);
-            float rs = 0.f;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const float pv = (s[cb][r] == -INFINITY) ? 0.f : __expf(s[cb][r] - m_new);
-                s[cb][r] = pv;
-                rs += pv;
-            }
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) rs += __shfl_xor(rs, off);
-            l_run[r] = l_run[r] * alpha[r] + rs;
-            m_run[r] = m_new;
-        }
-#pragma unroll
-        for (int i = 0; i < CB; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[i][r] *= alpha[r];
-        // ---- P -> LDS (per-wave image [query][key], bf16 hi/lo)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                __bf16 hh, ll;
-                split_bf16(s[cb][r], hh, ll);
-                const int off = (4 * (lane >> 4) + r) * PROW + (cb * 16 + (lane & 15)) * 2;
-                *reinterpret_cast<__bf16*>(p_hi + off) = hh;
-                *reinterpret_cast<__bf16*>(p_lo + off) = ll;
-            }
-        __syncthreads();
-        // ---- O += P V   (A = P: row = query l&15, k = key; B = V^T rows = channel)
-#pragma unroll
-        for (int ks = 0; ks < KTILE / 32; ++ks) {
-            Frag ph, pl;
-            const int poff = (lane & 15) * PROW + (ks * 4 + (lane >> 4)) * 16;
-            ph.u = *reinterpret_cast<const uint4*>(p_hi + poff);
-            pl.u = *reinterpret_cast<const uint4*>(p_lo + poff);
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                Frag vh, vl;
-                const int voff = (cb * 16 + (lane & 15)) * VROW + (ks * 4 + (lane >> 4)) * 16;
-                vh.u = *reinterpret_cast<const uint4*>(v_hi + voff);
-                vl.u = *reinterpret_cast<const uint4*>(v_lo + voff);
-                o[cb] = mfma_x3(ph.v, pl.v, vh.v, vl.v, o[cb]);
-            }
-        }
-    }
-    if (ksplit > 1) {   // ---- partial result: rows relative to this split's running maximum, with (m, l) behind them
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int q = q0 + 4 * (lane >> 4) + r;
-            if (q < T) {
-                float* pr = part + ((((size_t)b * H + h) * ksplit + ksid) * T + q) * (D + 4);   // (rows of D + 4 floats: 16-byte aligned)
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) pr[cb * 16 + (lane & 15)] = o[cb][r];
-                if ((lane & 15) == 0) { pr[D] = m_run[r]; pr[D + 1] = l_run[r]; }
-            }
-        }
-        return;
-    }
-    // ---- normalise and store
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int q = q0 + 4 * (lane >> 4) + r;
-        if (q < T) {
-            const float inv = 1.0f / l_run[r];
-            if (lse && (lane & 15) == 0) lse[((size_t)b * H + h) * T + q] = m_run[r] + __logf(l_run[r]);
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb)
-                out[((size_t)b * T + q) * (H * D) + h * D + cb * 16 + (lane & 15)] = o[cb][r] * inv;
-        }
-    }
-}
-
-// out[b, q, h D + c] = sum_s o_s[c] e^(m_s - M) / sum_s l_s e^(m_s - M), M = max_s m_s; one thread per (row, 4 channels)
-template <int D>
-__global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ part, float* __restrict__ out, float* __restrict__ lse,
-                                                           int T, int H, int ksplit, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c4 = (int)(i % (D / 4));
-    size_t row = i / (D / 4);
-    const int q = (int)(row % T); row /= T;
-    const int h = (int)(row % H);
-    const int b = (int)(row / H);
-    const float* pr = part + ((((size_t)b * H + h) * ksplit) * T + q) * (D + 4);
-    const size_t stride = (size_t)T * (D + 4);
-    float M = -INFINITY;
-    for (int s = 0; s < ksplit; ++s) M = fmaxf(M, pr[s * stride + D]);
-    float L = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int s = 0; s < ksplit; ++s) {
-        const float w = __expf(pr[s * stride + D] - M);
-        L += pr[s * stride + D + 1] * w;
-        const float4 o = *reinterpret_cast<const float4*>(pr + s * stride + 4 * c4);
-        acc.x += o.x * w; acc.y += o.y * w; acc.z += o.z * w; acc.w += o.w * w;
-    }
-    const float inv = 1.0f / L;
-    *reinterpret_cast<float4*>(out + ((size_t)b * T + q) * (H * D) + h * D + 4 * c4) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-    if (lse && c4 == 0) lse[((size_t)b * H + h) * T + q] = M + __logf(L);
-}
-
-constexpr int ATT_KSPLIT_MAX = 8;
-
-template <int D>
-int launch_attn(const float* qkv, float* out, float* lse, int B, int T, int H, hipStream_t stream, void* workspace = nullptr) {
-    constexpr int KROW = D * 2 + 16, VROW = KTILE * 2 + 16, PROW = KTILE * 2 + 16;
-    const size_t sh = 2 * KTILE * KROW + 2 * D * VROW + 4 * 2 * 16 * PROW;
-    if (sh > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    const int nqt = (T + QT - 1) / QT, nkt = (T + KTILE - 1) / KTILE;
-    const float scale = (float)(1.0 / sqrt(sqrt((double)D)));  // blocks.py:173 (python double, then fp32)
-    // key split (needs the workspace): where the grid would leave most of the chip idle -- under 128 workgroups for 256 compute units
-    // -- deal the key tiles over as many workgroups as bring it to ~256
-    int ksplit = 1;
-    const int wgs = B * H * nqt;
-    if (workspace && wgs < 128) {
-        ksplit = 256 / wgs;
-        if (ksplit > nkt) ksplit = nkt;
-        if (ksplit > ATT_KSPLIT_MAX) ksplit = ATT_KSPLIT_MAX;
-        if (ksplit < 1) ksplit = 1;
-    }
-    float* part = reinterpret_cast<float*>(workspace);
-    hipLaunchKernelGGL(attention_kernel<D>, dim3(wgs * ksplit), dim3(256), sh, stream, qkv, out, lse, T, H, scale, ksplit, part);
-    TQ_CHECK_LAUNCH();
-    if (ksplit > 1) {
-        const size_t n = (size_t)B * H * T * (D / 4);
-        hipLaunchKernelGGL(attn_combine_kernel<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part, out, lse, T, H, ksplit, n);
-        TQ_CHECK_LAUNCH();
-    }
-    return 0;
-}
-}  // namespace
+// The first-generation kernels -- forward with key split, combine, delta, dQ and dK / dV passes -- live in attention_g1.hpp and are
+// instantiated here with PAD = false (the head size is the tile); attention_hd.hip instantiates the same text with PAD = true for
+// every other head size.  The data layout and the flash structure are described at the top of that header.
+#include "attention_g1.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // Forward, second generation (used when the caller supplies a workspace):
@@ -309,14 +30,6 @@ int launch_attn(const float* qkv, float* out, float* lse, int B, int T, int H, h
 #define ATT_QB 2  // 16-query blocks per wave of the forward kernel
 #endif
 namespace {
-typedef short s16x4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr_read_f(const unsigned char* p) {
-    s16x4f v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4f*)(p));
-    union { s16x4f s; uint2 u; } c;
-    c.s = v;
-    return c.u;
-}
-
 // kv[b][h][plane][t][d] (bf16), planes: 0 K hi, 1 K lo, 2 V hi, 3 V lo; rows t >= T are zero
 __global__ void attn_prep_kernel(const float* __restrict__ qkv, unsigned char* __restrict__ kv, int T, int Tp, int H, int D,
                                  float scale, size_t n) {
@@ -589,8 +302,8 @@ __global__ __launch_bounds__(256, 2) void attention_fwd2_kernel(const float* __r
                 for (int cb = 0; cb < CB; ++cb) {
                     Frag bh, bl;
                     const int off = vrow * ROWB + (cb * 16 + 4 * (lane & 3)) * 2;
-                    bh.h[0] = tr_read_f(v_hi + off); bh.h[1] = tr_read_f(v_hi + off + 16 * ROWB);
-                    bl.h[0] = tr_read_f(v_lo + off); bl.h[1] = tr_read_f(v_lo + off + 16 * ROWB);
+                    bh.h[0] = tr_read(v_hi + off); bh.h[1] = tr_read(v_hi + off + 16 * ROWB);
+                    bl.h[0] = tr_read(v_lo + off); bl.h[1] = tr_read(v_lo + off + 16 * ROWB);
 #pragma unroll
                     for (int qb = 0; qb < QB; ++qb) {
                         o[qb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8a, bh.u), __builtin_bit_cast(f16x8a, ph[qb].u), o[qb][cb], 0, 0, 0);
@@ -619,8 +332,8 @@ __global__ __launch_bounds__(256, 2) void attention_fwd2_kernel(const float* __r
 #ifdef TQ_ATT_ABL_NOLDS
                 bh.u = make_uint4(off, kt, off ^ 0x3f803f80, 0x3f803f80); bl.u = make_uint4(kt, off, 0x3c003c00, off);
 #else
-                bh.h[0] = tr_read_f(v_hi + off); bh.h[1] = tr_read_f(v_hi + off + 16 * ROWB);
-                bl.h[0] = tr_read_f(v_lo + off); bl.h[1] = tr_read_f(v_lo + off + 16 * ROWB);
+                bh.h[0] = tr_read(v_hi + off); bh.h[1] = tr_read(v_hi + off + 16 * ROWB);
+                bl.h[0] = tr_read(v_lo + off); bl.h[1] = tr_read(v_lo + off + 16 * ROWB);
 #endif
 #ifdef TQ_ATT_ABL_NOPV
                 for (int qb = 0; qb < QB; ++qb) o[qb][cb] += f32x4{bh.v[0], bl.v[1], bh.v[2], bl.v[3]} * (float)ph[qb].v[0] + f32x4{pl[qb].v[0], pl[qb].v[1], ph[qb].v[2], ph[qb].v[3]};
@@ -708,12 +421,12 @@ extern "C" int tq_attention_fwd(const float* qkv, float* out, float* lse, void* 
     if (workspace) {
         if (D == 64) return launch_attn2<64>(qkv, out, lse, workspace, B, T, H, stream);
         if (D == 32) return launch_attn2<32>(qkv, out, lse, workspace, B, T, H, stream);
-        if (D == 128) return launch_attn<128>(qkv, out, lse, B, T, H, stream, workspace);   // first-generation kernel (+ key split, round 6)
+        if (D == 128) return launch_fwd<128, false>(qkv, out, lse, workspace, B, T, H, D, stream);   // first-generation kernel (+ key split, round 6)
         return TQ_ERR_SHAPE;
     }
-    if (D == 64) return launch_attn<64>(qkv, out, lse, B, T, H, stream);
-    if (D == 32) return launch_attn<32>(qkv, out, lse, B, T, H, stream);
-    if (D == 128) return launch_attn<128>(qkv, out, lse, B, T, H, stream);
+    if (D == 64) return launch_fwd<64, false>(qkv, out, lse, nullptr, B, T, H, D, stream);
+    if (D == 32) return launch_fwd<32, false>(qkv, out, lse, nullptr, B, T, H, D, stream);
+    if (D == 128) return launch_fwd<128, false>(qkv, out, lse, nullptr, B, T, H, D, stream);
     return TQ_ERR_SHAPE;
 }
 
@@ -729,349 +442,8 @@ extern "C" int tq_attention_fwd_presplit(const float* qkv, const void* kv_planes
 }
 
 // =================================================================================================
-// Attention backward (flash-style recompute).  Per (b, head), with Qs = scale*Q, Ks = scale*K:
-//   S = Qs Ks^T,  P = exp(S - lse),  O = P V,   delta_i = sum_d dO[i,d] O[i,d]
-//   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - delta),  dQ = scale * dS Ks,  dK = scale * dS^T Qs
-// Pass A keeps 64 queries stationary and streams key tiles (dQ); pass B keeps 64 keys stationary and streams
-// query tiles (dK, dV).  No atomics; P is recomputed in each pass.  Operands whose MFMA k index is the LDS row
-// (key / query) are fetched with ds_read_b64_tr_b16 from the same row-major images the other products read.
-// =================================================================================================
-namespace {
-
-typedef short s16x4b __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr_read(const unsigned char* p) {
-    s16x4b v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4b*)(p));
-    union { s16x4b s; uint2 u; } c;
-    c.s = v;
-    return c.u;
-}
-
-__global__ void attn_delta_kernel(const float* __restrict__ o, const float* __restrict__ d_o, float* __restrict__ delta, int T,
-                                  int H, int D, size_t n) {
-    // one wave per (b, t, h) row would be wasteful for D <= 128: one thread per row, 16-byte loads
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int h = (int)(i % H);
-    const size_t bt = i / H;
-    const int t = (int)(bt % T);
-    const size_t b = bt / T;
-    const float4* po = reinterpret_cast<const float4*>(o + bt * (size_t)(H * D) + h * D);
-    const float4* pd = reinterpret_cast<const float4*>(d_o + bt * (size_t)(H * D) + h * D);
-    float a = 0.f;
-    for (int j = 0; j < D / 4; ++j) {
-        const float4 x = po[j], y = pd[j];
-        a += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    delta[(b * H + h) * T + t] = a;
-}
-
-// stage a [64 rows][D] fp32 tile (rows of `src` with row stride `rs`, optional scale) as bf16 hi/lo row-major images
-template <int D>
-__device__ __forceinline__ void stage_rows(const float* src, size_t rs, int row0, int T, float scale, unsigned char* hi,
-                                           unsigned char* lo, int ROWB) {
-    for (int i = threadIdx.x; i < 64 * (D / 4); i += 256) {
-        const int r = i / (D / 4), c4 = i % (D / 4);
-        float4 v = make_float4(0, 0, 0, 0);
-        if (row0 + r < T) v = *reinterpret_cast<const float4*>(src + (size_t)(row0 + r) * rs + 4 * c4);
-        const float u[4] = {v.x * scale, v.y * scale, v.z * scale, v.w * scale};
-        bf16x4 hv, lv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { __bf16 hh, ll; split_bf16(u[j], hh, ll); hv[j] = hh; lv[j] = ll; }
-        *reinterpret_cast<bf16x4*>(hi + r * ROWB + c4 * 8) = hv;
-        *reinterpret_cast<bf16x4*>(lo + r * ROWB + c4 * 8) = lv;
-    }
-}
-
-// A-operand fragments (row = l&15 of a 16-row block starting at row0, k = channel) straight from global memory
-template <int D>
-__device__ __forceinline__ void load_row_frags(const float* src, size_t rs, int row, bool ok, float scale, Frag (&fh)[D / 32],
-                                               Frag (&fl)[D / 32]) {
-    const int lane = threadIdx.x & 63;
-    const float* p = src + (size_t)(ok ? row : 0) * rs + 8 * (lane >> 4);
-#pragma unroll
-    for (int ks = 0; ks < D / 32; ++ks) {
-        float4 a = make_float4(0, 0, 0, 0), c = a;
-        if (ok) { a = *reinterpret_cast<const float4*>(p + ks * 32); c = *reinterpret_cast<const float4*>(p + ks * 32 + 4); }
-        const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { __bf16 hh, ll; split_bf16(v[j] * scale, hh, ll); fh[ks].v[j] = hh; fl[ks].v[j] = ll; }
-    }
-}
-
-// write a 16 x 64 accumulator tile set (4 column blocks) as bf16 hi/lo [row][col] image for use as an A operand
-__device__ __forceinline__ void acc_to_image(const f32x4 (&s)[4], unsigned char* hi, unsigned char* lo, int ROWB) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            __bf16 hh, ll;
-            split_bf16(s[cb][r], hh, ll);
-            const int off = (4 * (lane >> 4) + r) * ROWB + (cb * 16 + (lane & 15)) * 2;
-            *reinterpret_cast<__bf16*>(hi + off) = hh;
-            *reinterpret_cast<__bf16*>(lo + off) = ll;
-        }
-}
-
-// ---- pass A: dQ ------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
-                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                  float* __restrict__ dqkv, int T, int H, float scale) {
-    constexpr int KS = D / 32, CB = D / 16;
-    constexpr int ROWB = D * 2 + 16;
-    constexpr int PROW = 64 * 2 + 16;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    unsigned char* k_hi = lds;
-    unsigned char* k_lo = k_hi + 64 * ROWB;
-    unsigned char* v_hi = k_lo + 64 * ROWB;
-    unsigned char* v_lo = v_hi + 64 * ROWB;
-    unsigned char* p_base = v_lo + 64 * ROWB;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nqt = (T + 63) / 64;
-    int bid = xcd_group_id(blockIdx.x, nqt, gridDim.x / nqt);  // the tiles of one (b, h) share an XCD's L2
-    const int qt = bid % nqt; bid /= nqt;
-    const int h = bid % H;
-    const int b = bid / H;
-    const int C3 = 3 * H * D, C1 = H * D;
-    const float* base = qkv + (size_t)b * T * C3;
-    const int q0 = qt * 64 + wave * 16;
-    unsigned char* p_hi = p_base + wave * 2 * 16 * PROW;
-    unsigned char* p_lo = p_hi + 16 * PROW;
-
-    Frag qh[KS], ql[KS], gh[KS], gl[KS];
-    {
-        const int q = q0 + (lane & 15);
-        load_row_frags<D>(base + h * D, C3, q, q < T, scale, qh, ql);
-        load_row_frags<D>(d_o + (size_t)b * T * C1 + h * D, C1, q, q < T, 1.0f, gh, gl);
-    }
-    float lrow[4], drow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int q = q0 + 4 * (lane >> 4) + r;
-        lrow[r] = (q < T) ? lse[((size_t)b * H + h) * T + q] : 0.f;
-        drow[r] = (q < T) ? delta[((size_t)b * H + h) * T + q] : 0.f;
-    }
-    f32x4 dq[CB];
-#pragma unroll
-    for (int i = 0; i < CB; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nkt = (T + 63) / 64;
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int s0 = kt * 64;
-        __syncthreads();
-        stage_rows<D>(base + (H + h) * D, C3, s0, T, scale, k_hi, k_lo, ROWB);
-        stage_rows<D>(base + (2 * H + h) * D, C3, s0, T, 1.0f, v_hi, v_lo, ROWB);
-        __syncthreads();
-        f32x4 s[4], dp[4];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            s[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dp[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int key = cb * 16 + (lane & 15);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                Frag bh, bl;
-                const int off = key * ROWB + (ks * 4 + (lane >> 4)) * 16;
-                bh.u = *reinterpret_cast<const uint4*>(k_hi + off);
-                bl.u = *reinterpret_cast<const uint4*>(k_lo + off);
-                s[cb] = mfma_x3(qh[ks].v, ql[ks].v, bh.v, bl.v, s[cb]);
-                bh.u = *reinterpret_cast<const uint4*>(v_hi + off);
-                bl.u = *reinterpret_cast<const uint4*>(v_lo + off);
-                dp[cb] = mfma_x3(gh[ks].v, gl[ks].v, bh.v, bl.v, dp[cb]);
-            }
-        }
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const bool valid = (s0 + cb * 16 + (lane & 15)) < T;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pv = valid ? __expf(s[cb][r] - lrow[r]) : 0.f;
-                s[cb][r] = pv * (dp[cb][r] - drow[r]);  // dS
-            }
-        }
-        acc_to_image(s, p_hi, p_lo, PROW);
-        __syncthreads();
-        // dQ += dS Ks : A = dS image (row = query), B[k = key][col = d] via transposed reads of the K image
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            Frag ah, al;
-            const int poff = (lane & 15) * PROW + (ks * 4 + (lane >> 4)) * 16;
-            ah.u = *reinterpret_cast<const uint4*>(p_hi + poff);
-            al.u = *reinterpret_cast<const uint4*>(p_lo + poff);
-            const int krow = ks * 32 + 8 * (lane >> 4) + ((lane >> 2) & 3);
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                Frag bh, bl;
-                const int off = krow * ROWB + (cb * 16 + 4 * (lane & 3)) * 2;
-                bh.h[0] = tr_read(k_hi + off); bh.h[1] = tr_read(k_hi + off + 4 * ROWB);
-                bl.h[0] = tr_read(k_lo + off); bl.h[1] = tr_read(k_lo + off + 4 * ROWB);
-                dq[cb] = mfma_x3(ah.v, al.v, bh.v, bl.v, dq[cb]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int q = q0 + 4 * (lane >> 4) + r;
-        if (q < T) {
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb)
-                dqkv[((size_t)b * T + q) * C3 + h * D + cb * 16 + (lane & 15)] = dq[cb][r] * scale;
-        }
-    }
-}
-
-// ---- pass B: dK, dV --------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256, 2) void attention_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
-                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                   float* __restrict__ dqkv, int T, int H, float scale) {
-    constexpr int KS = D / 32, CB = D / 16;
-    constexpr int ROWB = D * 2 + 16;
-    constexpr int PROW = 64 * 2 + 16;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    unsigned char* q_hi = lds;
-    unsigned char* q_lo = q_hi + 64 * ROWB;
-    unsigned char* g_hi = q_lo + 64 * ROWB;
-    unsigned char* g_lo = g_hi + 64 * ROWB;
-    float* lq = reinterpret_cast<float*>(g_lo + 64 * ROWB);  // [64] lse of the query tile
-    float* dq_ = lq + 64;                                     // [64] delta of the query tile
-    unsigned char* p_base = reinterpret_cast<unsigned char*>(dq_ + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nkt = (T + 63) / 64;
-    int bid = xcd_group_id(blockIdx.x, nkt, gridDim.x / nkt);  // the tiles of one (b, h) share an XCD's L2
-    const int kt = bid % nkt; bid /= nkt;
-    const int h = bid % H;
-    const int b = bid / H;
-    const int C3 = 3 * H * D, C1 = H * D;
-    const float* base = qkv + (size_t)b * T * C3;
-    const int k0 = kt * 64 + wave * 16;
-    unsigned char* p_hi = p_base + wave * 4 * 16 * PROW;   // P^T image
-    unsigned char* p_lo = p_hi + 16 * PROW;
-    unsigned char* s_hi = p_lo + 16 * PROW;                // dS^T image
-    unsigned char* s_lo = s_hi + 16 * PROW;
-
-    Frag kh[KS], kl[KS], vh[KS], vl[KS];
-    {
-        const int key = k0 + (lane & 15);
-        load_row_frags<D>(base + (H + h) * D, C3, key, key < T, scale, kh, kl);
-        load_row_frags<D>(base + (2 * H + h) * D, C3, key, key < T, 1.0f, vh, vl);
-    }
-    f32x4 dk[CB], dv[CB];
-#pragma unroll
-    for (int i = 0; i < CB; ++i) { dk[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-    const int nqt = (T + 63) / 64;
-    for (int qt = 0; qt < nqt; ++qt) {
-        const int q0 = qt * 64;
-        __syncthreads();
-        stage_rows<D>(base + h * D, C3, q0, T, scale, q_hi, q_lo, ROWB);
-        stage_rows<D>(d_o + (size_t)b * T * C1 + h * D, C1, q0, T, 1.0f, g_hi, g_lo, ROWB);
-        if (tid < 64) {
-            const bool ok = (q0 + tid) < T;
-            lq[tid] = ok ? lse[((size_t)b * H + h) * T + q0 + tid] : 0.f;
-            dq_[tid] = ok ? delta[((size_t)b * H + h) * T + q0 + tid] : 0.f;
-        }
-        __syncthreads();
-        // S^T = Ks Qs^T,  dP^T = V dO^T   (16 keys x 64 queries)
-        f32x4 s[4], dp[4];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            s[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dp[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int qq = cb * 16 + (lane & 15);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                Frag bh, bl;
-                const int off = qq * ROWB + (ks * 4 + (lane >> 4)) * 16;
-                bh.u = *reinterpret_cast<const uint4*>(q_hi + off);
-                bl.u = *reinterpret_cast<const uint4*>(q_lo + off);
-                s[cb] = mfma_x3(kh[ks].v, kl[ks].v, bh.v, bl.v, s[cb]);
-                bh.u = *reinterpret_cast<const uint4*>(g_hi + off);
-                bl.u = *reinterpret_cast<const uint4*>(g_lo + off);
-                dp[cb] = mfma_x3(vh[ks].v, vl[ks].v, bh.v, bl.v, dp[cb]);
-            }
-        }
-        f32x4 ds[4];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const int qq = cb * 16 + (lane & 15);
-            const bool valid = (q0 + qq) < T;
-            const float lv = lq[qq], dl = dq_[qq];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pv = valid ? __expf(s[cb][r] - lv) : 0.f;
-                s[cb][r] = pv;
-                ds[cb][r] = pv * (dp[cb][r] - dl);
-            }
-        }
-        acc_to_image(s, p_hi, p_lo, PROW);
-        acc_to_image(ds, s_hi, s_lo, PROW);
-        __syncthreads();
-        // dV += P^T dO,  dK += dS^T Qs : B[k = query][col = d] via transposed reads of the dO / Q images
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            Frag ph, pl, sh_, sl_;
-            const int poff = (lane & 15) * PROW + (ks * 4 + (lane >> 4)) * 16;
-            ph.u = *reinterpret_cast<const uint4*>(p_hi + poff);
-            pl.u = *reinterpret_cast<const uint4*>(p_lo + poff);
-            sh_.u = *reinterpret_cast<const uint4*>(s_hi + poff);
-            sl_.u = *reinterpret_cast<const uint4*>(s_lo + poff);
-            const int qrow = ks * 32 + 8 * (lane >> 4) + ((lane >> 2) & 3);
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                Frag bh, bl;
-                const int off = qrow * ROWB + (cb * 16 + 4 * (lane & 3)) * 2;
-                bh.h[0] = tr_read(g_hi + off); bh.h[1] = tr_read(g_hi + off + 4 * ROWB);
-                bl.h[0] = tr_read(g_lo + off); bl.h[1] = tr_read(g_lo + off + 4 * ROWB);
-                dv[cb] = mfma_x3(ph.v, pl.v, bh.v, bl.v, dv[cb]);
-                bh.h[0] = tr_read(q_hi + off); bh.h[1] = tr_read(q_hi + off + 4 * ROWB);
-                bl.h[0] = tr_read(q_lo + off); bl.h[1] = tr_read(q_lo + off + 4 * ROWB);
-                dk[cb] = mfma_x3(sh_.v, sl_.v, bh.v, bl.v, dk[cb]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int key = k0 + 4 * (lane >> 4) + r;
-        if (key < T) {
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const size_t o = ((size_t)b * T + key) * C3 + cb * 16 + (lane & 15);
-                dqkv[o + (H + h) * D] = dk[cb][r] * scale;
-                dqkv[o + (2 * H + h) * D] = dv[cb][r];
-            }
-        }
-    }
-}
-
-template <int D>
-int launch_attn_bwd(const float* qkv, const float* out, const float* d_o, const float* lse, float* delta, float* dqkv, int B,
-                    int T, int H, hipStream_t stream) {
-    constexpr int ROWB = D * 2 + 16, PROW = 64 * 2 + 16;
-    const size_t n = (size_t)B * T * H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, out, d_o, delta, T, H, D, n);
-    TQ_CHECK_LAUNCH();
-    const float scale = (float)(1.0 / sqrt(sqrt((double)D)));
-    const int nt = (T + 63) / 64;
-    const size_t shA = 4 * 64 * ROWB + 4 * 2 * 16 * PROW;
-    const size_t shB = 4 * 64 * ROWB + 128 * sizeof(float) + 4 * 4 * 16 * PROW;
-    if (shA > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dq_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shA);
-    if (shB > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dkv_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shB);
-    hipLaunchKernelGGL(attention_bwd_dq_kernel<D>, dim3(B * H * nt), dim3(256), shA, stream, qkv, d_o, lse, delta, dqkv, T, H, scale);
-    TQ_CHECK_LAUNCH();
-    hipLaunchKernelGGL(attention_bwd_dkv_kernel<D>, dim3(B * H * nt), dim3(256), shB, stream, qkv, d_o, lse, delta, dqkv, T, H, scale);
-    TQ_CHECK_LAUNCH();
-    return 0;
-}
-}  // namespace
-
-
-// =================================================================================================
 // Attention backward, second generation (round 3; D = 32 / 64, used when the caller supplies a workspace).  Same mathematics as
-// the two passes above, restructured along the lines of attention_fwd2_kernel:
+// the two first-generation passes ("Attention backward" in attention_g1.hpp), restructured along the lines of attention_fwd2_kernel:
 //   * one prep pass writes the bf16 hi / lo planes [b][h][plane][Tp][D] of K (x scale), V and of Q (x scale log2 e), dO, and the
 //     row dots delta = dO . O; the main kernels' staging is then a 16-byte copy with the loads of tile i + 1 in flight under
 //     tile i (the first generation staged synchronously and re-split every tile in each of the T / 64 workgroups of a (b, h));
@@ -1251,8 +623,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd2_dq_kernel(const unsigne
             for (int cb = 0; cb < CB; ++cb) {
                 Frag bh, bl;
                 const int off = krow * ROWB + (cb * 16 + 4 * (lane & 3)) * 2;
-                bh.h[0] = tr_read_f(k_hi + off); bh.h[1] = tr_read_f(k_hi + off + 16 * ROWB);
-                bl.h[0] = tr_read_f(k_lo + off); bl.h[1] = tr_read_f(k_lo + off + 16 * ROWB);
+                bh.h[0] = tr_read(k_hi + off); bh.h[1] = tr_read(k_hi + off + 16 * ROWB);
+                bl.h[0] = tr_read(k_lo + off); bl.h[1] = tr_read(k_lo + off + 16 * ROWB);
 #pragma unroll
                 for (int qb = 0; qb < QB; ++qb) dq[qb][cb] = mfma_x3(bh.v, bl.v, sh[qb].v, sl[qb].v, dq[qb][cb]);
             }
@@ -1390,11 +762,11 @@ __global__ __launch_bounds__(256, 2) void attention_bwd2_dkv_kernel(const unsign
             for (int cb = 0; cb < CB; ++cb) {
                 Frag bh, bl;
                 const int off = qrow * ROWB + (cb * 16 + 4 * (lane & 3)) * 2;
-                bh.h[0] = tr_read_f(g_hi + off); bh.h[1] = tr_read_f(g_hi + off + 16 * ROWB);
-                bl.h[0] = tr_read_f(g_lo + off); bl.h[1] = tr_read_f(g_lo + off + 16 * ROWB);
+                bh.h[0] = tr_read(g_hi + off); bh.h[1] = tr_read(g_hi + off + 16 * ROWB);
+                bl.h[0] = tr_read(g_lo + off); bl.h[1] = tr_read(g_lo + off + 16 * ROWB);
                 dv[kb][cb] = mfma_x3(bh.v, bl.v, ph.v, pl.v, dv[kb][cb]);
-                bh.h[0] = tr_read_f(q_hi + off); bh.h[1] = tr_read_f(q_hi + off + 16 * ROWB);
-                bl.h[0] = tr_read_f(q_lo + off); bl.h[1] = tr_read_f(q_lo + off + 16 * ROWB);
+                bh.h[0] = tr_read(q_hi + off); bh.h[1] = tr_read(q_hi + off + 16 * ROWB);
+                bl.h[0] = tr_read(q_lo + off); bl.h[1] = tr_read(q_lo + off + 16 * ROWB);
                 dk[kb][cb] = mfma_x3(bh.v, bl.v, sh.v, sl.v, dk[kb][cb]);
             }
         }
@@ -1461,9 +833,9 @@ extern "C" int tq_attention_bwd(const float* qkv, const float* out, const float*
                                 float* dqkv, int B, int T, int H, int D, hipStream_t stream) {
     if (!qkv || !out || !dout || !lse || !delta || !dqkv) return TQ_ERR_ARG;
     if (B <= 0 || T <= 0 || H <= 0) return TQ_ERR_SHAPE;
-    if (D == 64) return launch_attn_bwd<64>(qkv, out, dout, lse, delta, dqkv, B, T, H, stream);
-    if (D == 32) return launch_attn_bwd<32>(qkv, out, dout, lse, delta, dqkv, B, T, H, stream);
-    if (D == 128) return launch_attn_bwd<128>(qkv, out, dout, lse, delta, dqkv, B, T, H, stream);
+    if (D == 64) return launch_bwd<64, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
+    if (D == 32) return launch_bwd<32, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
+    if (D == 128) return launch_bwd<128, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
     return TQ_ERR_SHAPE;
 }
 
