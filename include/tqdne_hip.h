@@ -239,14 +239,21 @@ int tq_conv1d_bwd_weight_colsum(const TqConvDesc* desc, const float* dy, const f
                                 float* colsum_c, float* colsum_c2, hipStream_t stream);
 
 /* First conv of the network: (B, C_in<=16, T) fp32 input, scaled per sample by in_scale[b] (EDM c_in, edm.py:107;
- * NULL = 1), k taps "same" -> (B, T, C_out) channels-last + bias (+ partial statistics).  unet.py:233. */
+ * NULL = 1), k taps "same" -> (B, T, C_out) channels-last + bias (+ partial statistics (B, ceil(T / 128), C_out, 2)).  unet.py:233.
+ * C_out: every multiple of 32 up to 1024 (channel-tiled kernel, csrc/ends_wide.hip) besides the powers of two 4 ... 1024 whose
+ * weights fit one workgroup's LDS (the first kernel, unchanged for those); k in {1, 3, 5}; any B, T >= 1. */
+/* LDS bytes tq_stem_conv_fwd needs for a shape; 0 = unsupported shape.  Needs no device. */
+size_t tq_stem_conv_lds_bytes(int C_in, int C_out, int ktaps);
 int tq_stem_conv_fwd(const float* x_nct, const float* in_scale, const float* w, const float* bias, float* y,
                      float* stats_partial, int B, int C_in, int T, int C_out, int ktaps, hipStream_t stream);
 
 /* Last conv: GroupNorm32+SiLU (folded scale/shift) -> conv k "same" to C_out<=16 -> (B, C_out, T) output,
  * then out = c_out[b] * conv + c_skip[b] * skip_src[b, co, t]  (EDM / consistency preconditioning, edm.py:111-113,
  * consistency_model.py:78); c_out/c_skip/skip_src NULL = plain conv output.  unet.py:355-357,398. */
-/* LDS bytes tq_head_conv_fwd needs for a shape; 0 = unsupported shape (16 | C_in <= 128, C_out <= 16, k in {1, 3, 5}, <= 64 KB). */
+/* C_in: 16 | C_in <= 128 where the first kernels' LDS tile fits 64 KB (unchanged for those shapes), and every multiple of 32 up to
+ * 1024 (csrc/ends_wide.hip: the reduction over C_in walks chunks of <= 128 channels inside the workgroup; input read once; fp32 FMA;
+ * no atomics; <= 64 KB of LDS); C_out <= 16; k in {1, 3, 5}; any B, T >= 1; with or without the prologue / the epilogue. */
+/* LDS bytes tq_head_conv_fwd needs for a shape; 0 = unsupported shape.  Needs no device. */
 size_t tq_head_conv_lds_bytes(int C_in, int C_out, int ktaps);
 int tq_head_conv_fwd(const float* x, const float* gscale, const float* gshift, const float* w, const float* bias,
                      const float* c_out, const float* c_skip, const float* skip_src, float* y_nct, int B, int T, int C_in,
@@ -317,7 +324,9 @@ int tq_pair_sum(const float* d_up, float* dx, int B, int T, int C, int accumulat
  * k = 3 conv): folds dw2 (2 C_out, C_in, 3) = [d even-phase taps | d odd-phase taps] back onto the conv's five taps, dw (C_out, C_in, 5)
  * (overwritten): dw0 = dA0 + dB0, dw1 = dA0 + dB1, dw2 = dA1 + dB1, dw3 = dA1 + dB2, dw4 = dA2 + dB2. */
 int tq_upsample_poly_wgrad_fold(const float* dw2, float* dw, int C_out, int C_in, hipStream_t stream);
-/* stem conv weight gradient (atomically added into zeroed dw (C_out, C_in, K)) */
+/* stem conv weight gradient (atomically added into zeroed dw (C_out, C_in, K)).  Keeps its limit of C_out C_in K <= 2048 weights
+ * (TQ_ERR_SHAPE beyond): the plans form the gradient of a wider stem with tq_conv1d_bwd_weight on a 32-channel channels-last copy of
+ * the input (bf16x3 error bars), whatever the first-level width. */
 int tq_stem_conv_bwd_weight(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in, int T,
                             int C_out, int ktaps, hipStream_t stream);
 /* ABI 5: the same two with a scratch buffer of tq_stem_head_bwd_workspace() bytes (own buffer per call site and stream): every
@@ -330,8 +339,14 @@ int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, const float*
 int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, const float* x, const float* gscale, const float* gshift,
                         const float* w, float* g_out, float* gstats_partial, float* dw, float* db, int B, int T, int C_in,
                         int C_out, int ktaps, void* workspace, size_t ws_bytes, hipStream_t stream);
-/* head conv backward: dF = c_out[b]*dpred; g_out (B,T,C_in) = (W^T*dF)*silu'(gscale*x+gshift) with GN partial sums;
- * dw, db atomically added (zero them first) */
+/* head conv backward: dF = c_out[b]*dpred; g_out (B,T,C_in) = (W^T*dF)*silu'(gscale*x+gshift) with GN partial sums
+ * {sum g, sum g x} per channel and 128-position slot; dw, db atomically added (zero them first).
+ * C_in: the powers of two 8 ... 256 (first kernels, unchanged) and every multiple of 32 up to 1024 (csrc/ends_wide.hip: a grid
+ * dimension over chunks of <= 128 input channels, exact fp32 like the first kernels); C_out <= 16; k in {1, 3, 5}.  The _ws form
+ * with the fixed tq_stem_head_bwd_workspace() bytes serves every such shape: the chunked kernel launches no more workgroups per
+ * chunk than partial rows of C_out C_in k + 16 floats fit the workspace it is given (25 at 1024 x 16 x 5). */
+/* LDS bytes tq_head_conv_bwd(_ws) needs for a shape; 0 = unsupported shape.  Needs no device. */
+size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps);
 int tq_head_conv_bwd(const float* dpred_nct, const float* c_out, const float* x, const float* gscale, const float* gshift,
                      const float* w, float* g_out, float* gstats_partial, float* dw, float* db, int B, int T, int C_in,
                      int C_out, int ktaps, hipStream_t stream);

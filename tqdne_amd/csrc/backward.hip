@@ -6,6 +6,7 @@
 //   * stem weight gradient and head (last conv) backward
 #include <cstdlib>
 #include "common.hpp"
+#include "ends_wide.hpp"
 #include "../../include/tqdne_hip.h"
 
 using namespace tq;
@@ -1650,6 +1651,21 @@ extern "C" int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, c
     return 0;
 }
 
+// dynamic LDS of the kernel tq_head_conv_bwd(_ws) launches for a shape, 0 = not built for it: the launcher's conditions, in its order
+extern "C" size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps) {
+    if (ktaps != 1 && ktaps != 3 && ktaps != 5) return 0;
+    if (!(C_in < 8 || C_in % 8 || 256 % (C_in / 4) || C_out < 1 || C_out > 16)) {
+        if (C_out <= 8 && ktaps == 5 && C_in >= 32 && C_in <= 256 && 256 % C_in == 0) {
+            const int mco = C_out <= 4 ? 4 : 8;
+            return ((size_t)mco * (STAT_SLOT + 4) + (size_t)256 * mco * 5) * sizeof(float);
+        }
+        const int maxco = C_out <= 4 ? 4 : 16, nrow = 256 / (C_in / 4);
+        const size_t sh = ((size_t)maxco * (STAT_SLOT + ktaps - 1) + (size_t)C_in * (STAT_SLOT + ktaps) + (size_t)nrow * C_in * 2) * sizeof(float);
+        if (sh <= 160 * 1024) return sh;
+    }
+    return ends_wide_head_bwd_lds(C_in, C_out, ktaps);
+}
+
 extern "C" int tq_head_conv_bwd(const float* dpred_nct, const float* c_out, const float* x, const float* gscale,
                                 const float* gshift, const float* w, float* g_out, float* gstats, float* dw, float* db, int B,
                                 int T, int C_in, int C_out, int ktaps, hipStream_t stream) {
@@ -1661,7 +1677,9 @@ extern "C" int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, c
                                    int T, int C_in, int C_out, int ktaps, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!dpred_nct || !x || !w || !g_out || !dw || !db) return TQ_ERR_ARG;
     if ((gscale == nullptr) != (gshift == nullptr)) return TQ_ERR_ARG;
-    if (B <= 0 || T <= 0 || C_in < 8 || C_in % 8 || 256 % (C_in / 4) || C_out < 1 || C_out > 16) return TQ_ERR_SHAPE;
+    // (what the kernels here are not built for goes to the channel-chunked kernel of ends_wide.hip, which answers TQ_ERR_SHAPE for the rest)
+    if (B <= 0 || T <= 0 || C_in < 8 || C_in % 8 || 256 % (C_in / 4) || C_out < 1 || C_out > 16)
+        return ends_wide_head_bwd(dpred_nct, c_out, x, gscale, gshift, w, g_out, gstats, dw, db, B, T, C_in, C_out, ktaps, workspace, ws_bytes, stream);
     const int maxco = C_out <= 4 ? 4 : 16;
     const int nslots = (T + STAT_SLOT - 1) / STAT_SLOT;
     if (C_out <= 8 && ktaps == 5 && C_in >= 32 && C_in <= 256 && 256 % C_in == 0) {   // the streaming form (round 4; 5 ... 8 channels: round 5)
@@ -1691,7 +1709,8 @@ extern "C" int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, c
     }
     const int nrow = 256 / (C_in / 4);
     const size_t sh = ((size_t)maxco * (STAT_SLOT + ktaps - 1) + (size_t)C_in * (STAT_SLOT + ktaps) + (size_t)nrow * C_in * 2) * sizeof(float);
-    if (sh > 160 * 1024) return TQ_ERR_SHAPE;
+    if (sh > 160 * 1024)
+        return ends_wide_head_bwd(dpred_nct, c_out, x, gscale, gshift, w, g_out, gstats, dw, db, B, T, C_in, C_out, ktaps, workspace, ws_bytes, stream);
 #define TQ_HB(K)                                                                                             \
     {                                                                                                        \
         auto kern = (maxco == 4) ? head_bwd_kernel<K, 4> : head_bwd_kernel<K, 16>;                                                                    \

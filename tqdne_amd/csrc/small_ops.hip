@@ -4,6 +4,7 @@
 // 16-byte coalesced accesses; none is GEMM-shaped enough to be worth MFMA.
 #include "common.hpp"
 #include "gn_fold.hpp"
+#include "ends_wide.hpp"
 #include "../../include/tqdne_hip.h"
 
 using namespace tq;
@@ -152,11 +153,13 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
 extern "C" int tq_stem_conv_fwd(const float* x, const float* in_scale, const float* w, const float* bias, float* y,
                                 float* stats, int B, int C_in, int T, int C_out, int ktaps, hipStream_t stream) {
     if (!x || !w || !y) return TQ_ERR_ARG;
-    if (B <= 0 || T <= 0 || C_in <= 0 || C_in > 16 || C_out < 4 || C_out % 4 || C_out > 1024 || 256 % (C_out / 4)) return TQ_ERR_SHAPE;
+    // (what this kernel is not built for goes to the channel-tiled kernel of ends_wide.hip, which answers TQ_ERR_SHAPE for the rest)
+    if (B <= 0 || T <= 0 || C_in <= 0 || C_in > 16 || C_out < 4 || C_out % 4 || C_out > 1024 || 256 % (C_out / 4))
+        return ends_wide_stem_fwd(x, in_scale, w, bias, y, stats, B, C_in, T, C_out, ktaps, stream);
     const int nslots = (T + STAT_SLOT - 1) / STAT_SLOT;
     const int ngrp = C_out / 4, nrow = 256 / ngrp;
     const size_t sh = ((size_t)C_in * (STAT_SLOT + ktaps - 1) + (size_t)ktaps * C_in * C_out + (size_t)nrow * C_out * 2) * sizeof(float);
-    if (sh > 160 * 1024) return TQ_ERR_SHAPE;
+    if (sh > 160 * 1024) return ends_wide_stem_fwd(x, in_scale, w, bias, y, stats, B, C_in, T, C_out, ktaps, stream);
 #define TQ_STEM(K)                                                                                          \
     {                                                                                                       \
         auto kern = stem_conv_kernel<K>;                                                                    \
@@ -412,7 +415,21 @@ static size_t head_conv_lds(int C_in, int C_out, int ktaps) {
     return sh > 64 * 1024 ? 0 : sh;
 }
 
-extern "C" size_t tq_head_conv_lds_bytes(int C_in, int C_out, int ktaps) { return head_conv_lds(C_in, C_out, ktaps); }
+extern "C" size_t tq_head_conv_lds_bytes(int C_in, int C_out, int ktaps) {
+    const size_t sh = head_conv_lds(C_in, C_out, ktaps);
+    return sh ? sh : ends_wide_head_fwd_lds(C_in, C_out, ktaps);   // (the launcher's order: the kernels above, else the chunked one)
+}
+
+// the same question for tq_stem_conv_fwd: the conditions of its launcher, in its order
+extern "C" size_t tq_stem_conv_lds_bytes(int C_in, int C_out, int ktaps) {
+    if (ktaps != 1 && ktaps != 3 && ktaps != 5) return 0;
+    if (!(C_in <= 0 || C_in > 16 || C_out < 4 || C_out % 4 || C_out > 1024 || 256 % (C_out / 4))) {
+        const int nrow = 256 / (C_out / 4);
+        const size_t sh = ((size_t)C_in * (STAT_SLOT + ktaps - 1) + (size_t)ktaps * C_in * C_out + (size_t)nrow * C_out * 2) * sizeof(float);
+        if (sh <= 160 * 1024) return sh;
+    }
+    return ends_wide_stem_lds(C_in, C_out, ktaps);
+}
 
 extern "C" int tq_head_conv_fwd(const float* x, const float* gscale, const float* gshift, const float* w, const float* bias,
                                 const float* c_out, const float* c_skip, const float* skip_src, float* y, int B, int T,
@@ -421,7 +438,8 @@ extern "C" int tq_head_conv_fwd(const float* x, const float* gscale, const float
     if ((gscale == nullptr) != (gshift == nullptr)) return TQ_ERR_ARG;
     if (c_out && (!c_skip || !skip_src)) return TQ_ERR_ARG;
     const size_t sh = head_conv_lds(C_in, C_out, ktaps);
-    if (B <= 0 || T <= 0 || sh == 0) return TQ_ERR_SHAPE;
+    if (B <= 0 || T <= 0) return TQ_ERR_SHAPE;
+    if (sh == 0) return ends_wide_head_fwd(x, gscale, gshift, w, bias, c_out, c_skip, skip_src, y, B, T, C_in, C_out, ktaps, stream);   // (chunked over C_in)
     if ((C_out <= 4 || C_out == 6 || C_out == 8 || C_out == 16) && (C_in == 16 || C_in == 32 || C_in == 64 || C_in == 128)) {
         const int nt = (T + (64 - (ktaps - 1)) - 1) / (64 - (ktaps - 1));
         const int per = C_out <= 8 ? C_out : 8;   // output channels per launch (16 = two launches of 8: the input tile is staged twice)

@@ -246,13 +246,29 @@ def _recorded_event():
     return e
 
 
-def _check_head_limits(C_in: int, C_out: int, k: int):
+def _check_head_limits(C_in: int, C_out: int, k: int, name: str = "out.2"):
     """The limits of tq_head_conv_fwd, asked of the library itself (tq_head_conv_lds_bytes: 0 = not built for the shape) when the
     plan is built, so that an unsupported model fails at construction with a message rather than at its first forward."""
     if _lib.load().tq_head_conv_lds_bytes(C_in, C_out, k) == 0:
         raise NotImplementedError(
-            f"output conv {C_in} -> {C_out} channels, k = {k}: the HIP head kernel takes 16 | C_in <= 128, C_out <= 16, k in (1, 3, 5) "
-            "and <= 64 KB of LDS")
+            f"output conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP head kernels take C_in = 16, 32, 48, ... 128 or a multiple of "
+            "32 up to 1024, C_out <= 16 and k in (1, 3, 5)")
+
+
+def _check_stem_limits(C_in: int, C_out: int, k: int, name: str = "input_blocks.0.0"):
+    """The same for tq_stem_conv_fwd (tq_stem_conv_lds_bytes)."""
+    if _lib.load().tq_stem_conv_lds_bytes(C_in, C_out, k) == 0:
+        raise NotImplementedError(
+            f"input conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP stem kernels take C_in <= 16, C_out a multiple of 32 up to "
+            "1024 (or a power of two from 4) and k in (1, 3, 5)")
+
+
+def _check_head_bwd_limits(C_in: int, C_out: int, k: int, name: str = "out.2"):
+    """The same for tq_head_conv_bwd (tq_head_conv_bwd_lds_bytes), asked when a training plan is built."""
+    if _lib.load().tq_head_conv_bwd_lds_bytes(C_in, C_out, k) == 0:
+        raise NotImplementedError(
+            f"backward of output conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP head backward kernels take C_in a power of two "
+            "from 8 to 256 or a multiple of 32 up to 1024, C_out <= 16 and k in (1, 3, 5)")
 
 
 def _check_width_limits(name: str, C_in: int, C_out: int):
@@ -617,6 +633,7 @@ class UNetEngine:
 
         # stem (dynamic args: x, in_scale) -------------------------------------------------------
         stem = m.input_blocks[0][0]
+        _check_stem_limits(m.in_channels, stem.out_channels, stem.kernel_size[0])
         self.stem_out = self._act(stem.out_channels, T, True)
         hs = [self.stem_out]
         h = self.stem_out
@@ -1075,6 +1092,7 @@ class SeqEngine(UNetEngine):
         stem = m.input_layer
         if stem.in_channels > 16:
             raise NotImplementedError("input layer with more than 16 channels")
+        _check_stem_limits(stem.in_channels, stem.out_channels, stem.kernel_size[0], "input_layer")
         self.stem_out = self._act(stem.out_channels, T, True)
         h = self.stem_out
         blocks = getattr(m, m.blocks_attr)
@@ -1099,6 +1117,7 @@ class SeqEngine(UNetEngine):
         out = m.output_layer
         self.out_nct = self._empty(B, out.out_channels, h.T)
         if out.out_channels <= 16:
+            _check_head_limits(h.C, out.out_channels, out.kernel_size[0], "output_layer")
             self.out_mode = "head"
         else:  # wide output (encoder: 2 x latent channels): fused conv to channels-last, then a layout flip
             self.out_mode = "conv"

@@ -353,6 +353,8 @@ class BackwardPlan:
         # ---- head
         final = e.final
         head = m.out[2]
+        from .engine import _check_head_bwd_limits
+        _check_head_bwd_limits(final.C, m.out_channels, head.kernel_size[0])
         Gh = self.scratch("G", final.T, final.C)
         gst = self._empty(B, _nslots(final.T), final.C, 2)
         # (scratch for the two-stage sums of the head / stem weight gradients: one buffer each, see tq_stem_head_bwd_workspace)
@@ -805,7 +807,7 @@ class SeqBackwardPlan(BackwardPlan):
 
     def _build(self):
         from ._lib import TqConvDesc
-        from .engine import Act, ConvRec, ConvSite
+        from .engine import Act, ConvRec, ConvSite, _check_head_bwd_limits
         e, m, lib, B = self.e, self.m, self.lib, self.B
         self._wgrad_ops = []
         self._grad_writer = {}   # data_ptr of a gradient tensor -> (op entry of its last writer so far,)
@@ -816,6 +818,7 @@ class SeqBackwardPlan(BackwardPlan):
         final, out = e.final, m.output_layer
         dfin = self.grad(final)
         if e.out_mode == "head":   # narrow output (decoder): VALU kernel straight from the NCW gradient
+            _check_head_bwd_limits(final.C, out.out_channels, out.kernel_size[0], "output_layer")
             nws = lib.tq_stem_head_bwd_workspace()
             self._ws_head = torch.empty(nws, dtype=torch.uint8, device=self.dev)
             self.head_op = [lib.tq_head_conv_bwd_ws, [None, None, _p(final.buf), None, None, _p(out.weight), _p(dfin), None,

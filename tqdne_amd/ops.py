@@ -115,22 +115,27 @@ def gn_finalize(stats0, C0, T, gamma, beta, stats1=None, C1=0, slot0=0, slot1=0)
     return gs, gh, mr
 
 
-def stem_conv(x_nct, weight, bias, in_scale=None, stats=True):
+def stem_conv(x_nct, weight, bias, in_scale=None, stats=True, out=None):
+    """``out``: caller-owned (y (B, T, C_out), statistics (B, ceil(T / 128), C_out, 2)) to write into"""
     lib = _lib.load()
     B, Cin, T = x_nct.shape
     Cout, _, K = weight.shape
-    y = torch.empty(B, T, Cout, device=x_nct.device)
-    st = torch.empty(B, nslots(T), Cout, 2, device=x_nct.device) if stats else None
+    if out is not None:
+        y, st = out
+    else:
+        y = torch.empty(B, T, Cout, device=x_nct.device)
+        st = torch.empty(B, nslots(T), Cout, 2, device=x_nct.device) if stats else None
     check(lib.tq_stem_conv_fwd(_p(x_nct.contiguous()), _p(in_scale), _p(weight.contiguous()), _p(bias), _p(y), _p(st), B, Cin,
                                T, Cout, K, _stream(x_nct.device)), "stem")
     return y, st
 
 
-def head_conv(x, weight, bias, gscale=None, gshift=None, c_out=None, c_skip=None, skip_src=None):
+def head_conv(x, weight, bias, gscale=None, gshift=None, c_out=None, c_skip=None, skip_src=None, out=None):
+    """``out``: caller-owned (B, C_out, T) tensor to write into"""
     lib = _lib.load()
     B, T, Cin = x.shape
     Cout, _, K = weight.shape
-    y = torch.empty(B, Cout, T, device=x.device)
+    y = torch.empty(B, Cout, T, device=x.device) if out is None else out
     check(lib.tq_head_conv_fwd(_p(x), _p(gscale), _p(gshift), _p(weight.contiguous()), _p(bias), _p(c_out), _p(c_skip),
                                _p(skip_src), _p(y), B, T, Cin, Cout, K, _stream(x.device)), "head")
     return y
@@ -369,13 +374,17 @@ def stem_conv_bwd_weight(dy, x_nct, wshape, in_scale=None, workspace=True):
     return dw
 
 
-def head_conv_bwd(dpred_nct, x, weight, gscale=None, gshift=None, c_out=None, stats=True, workspace=True):
+def head_conv_bwd(dpred_nct, x, weight, gscale=None, gshift=None, c_out=None, stats=True, workspace=True, out=None):
+    """``out``: caller-owned (G (B, T, C_in), GN partial sums (B, ceil(T / 128), C_in, 2), dw, db); dw and db are ADDED to (zero them)"""
     lib = _lib.load()
     B, T, Cin = x.shape
     Cout, _, K = weight.shape
-    g = torch.empty_like(x)
-    st = torch.empty(B, nslots(T), Cin, 2, device=x.device) if stats else None
-    dw, db = torch.zeros_like(weight), torch.zeros(Cout, device=x.device)
+    if out is not None:
+        g, st, dw, db = out
+    else:
+        g = torch.empty_like(x)
+        st = torch.empty(B, nslots(T), Cin, 2, device=x.device) if stats else None
+        dw, db = torch.zeros_like(weight), torch.zeros(Cout, device=x.device)
     ws = torch.empty(lib.tq_stem_head_bwd_workspace(), dtype=torch.uint8, device=x.device) if workspace else None
     check(lib.tq_head_conv_bwd_ws(_p(dpred_nct), _p(c_out), _p(x), _p(gscale), _p(gshift), _p(weight.contiguous()), _p(g), _p(st),
                                   _p(dw), _p(db), B, T, Cin, Cout, K, _p(ws), 0 if ws is None else ws.numel(), _stream(x.device)), "head bwd")
