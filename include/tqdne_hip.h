@@ -238,7 +238,8 @@ int tq_conv1d_bwd_weight_colsum(const TqConvDesc* desc, const float* dy, const f
                                 const float* gshift, float* dw, void* workspace, size_t ws_bytes, float* colsum_bc, int bc_stride,
                                 float* colsum_c, float* colsum_c2, hipStream_t stream);
 
-/* First conv of the network: (B, C_in<=16, T) fp32 input, scaled per sample by in_scale[b] (EDM c_in, edm.py:107;
+/* First conv of the network: (B, C_in<=16, T) fp32 input (this kernel's limit; the plans route stems of 17 ... 64 signal channels
+ * through tq_nct_to_btc + tq_conv1d_fwd, see the boundary section below), scaled per sample by in_scale[b] (EDM c_in, edm.py:107;
  * NULL = 1), k taps "same" -> (B, T, C_out) channels-last + bias (+ partial statistics (B, ceil(T / 128), C_out, 2)).  unet.py:233.
  * C_out: every multiple of 32 up to 1024 (channel-tiled kernel, csrc/ends_wide.hip) besides the powers of two 4 ... 1024 whose
  * weights fit one workgroup's LDS (the first kernel, unchanged for those); k in {1, 3, 5}; any B, T >= 1. */
@@ -247,7 +248,8 @@ size_t tq_stem_conv_lds_bytes(int C_in, int C_out, int ktaps);
 int tq_stem_conv_fwd(const float* x_nct, const float* in_scale, const float* w, const float* bias, float* y,
                      float* stats_partial, int B, int C_in, int T, int C_out, int ktaps, hipStream_t stream);
 
-/* Last conv: GroupNorm32+SiLU (folded scale/shift) -> conv k "same" to C_out<=16 -> (B, C_out, T) output,
+/* Last conv: GroupNorm32+SiLU (folded scale/shift) -> conv k "same" to C_out<=16 (this kernel's limit; heads of 17 ... 64 signal
+ * channels run as tq_conv1d_fwd + tq_btc_to_nct, see the boundary section below) -> (B, C_out, T) output,
  * then out = c_out[b] * conv + c_skip[b] * skip_src[b, co, t]  (EDM / consistency preconditioning, edm.py:111-113,
  * consistency_model.py:78); c_out/c_skip/skip_src NULL = plain conv output.  unet.py:355-357,398. */
 /* C_in: 16 | C_in <= 128 where the first kernels' LDS tile fits 64 KB (unchanged for those shapes), and every multiple of 32 up to
@@ -470,6 +472,22 @@ int tq_vae_reparam_bwd(const float* enc, const float* eps, const float* dz, floa
 /* Stem input of a signal-conditioned model (edm.py:108-109): out (B, C0 + C1, T) = [x * scale[b] | cond_signal]; scale nullable. */
 int tq_concat_scale(const float* x, const float* scale, const float* cond_signal, float* out, int B, int C0, int C1, int T,
                     hipStream_t stream);
+
+/* ---- NCW <-> channels-last boundary of models with 17 ... 64 signal channels (csrc/boundary.hip) ---------- */
+/* The dedicated stem / head kernels above stop at 16 signal channels; a stem or head of 17 ... tq_boundary_max_channels() signal
+ * channels is an ordinary 32- / 64-channel contraction and runs as tq_conv1d_fwd / tq_conv1d_bwd_* on channels-last tensors padded to
+ * the 32-channel granule.  These two launches are the layout change on either side, with what the dedicated kernels fold into it
+ * (edm.py:105-113, consistency_model.py:63-78).  Any B, T >= 1; both go through an LDS tile of 64 positions; additive to ABI 8.
+ *   tq_boundary_max_channels(): 64 (needs no device).
+ *   tq_nct_to_btc: out (B, T, Cp), 32 | Cp >= C0 + C1 <= 64:  out[b, t, c] = x[b, c, t] * scale[b] for c < C0 (scale nullable = 1),
+ *     cond[b, c - C0, t] for C0 <= c < C0 + C1 (cond NULL iff C1 = 0), and exactly 0 for C0 + C1 <= c < Cp -- written on every call.
+ *   tq_btc_to_nct: y (B, C, T) = v[b, t, c_off + c] * a[b] + s[b] * skip_src[b, c, t] from v (B, T, Cp), 32 | Cp >= c_off + C,
+ *     C <= 64; a nullable (= 1); s and skip_src (B, C, T) both given or both NULL. */
+int tq_boundary_max_channels(void);
+int tq_nct_to_btc(const float* x_nct, const float* scale, const float* cond_nct, float* out_btc, int B, int C0, int C1, int T, int Cp,
+                  hipStream_t stream);
+int tq_btc_to_nct(const float* v_btc, const float* a, const float* s, const float* skip_src, float* y_nct, int B, int T, int Cp,
+                  int c_off, int C, hipStream_t stream);
 
 /* ---- optimizer (edm.py:240-251, ema.py:24-28) ------------------------------------------------------------- */
 /* One launch for the whole model: torch.optim.Adam's update (no weight decay, no amsgrad) on every chunk of the table,

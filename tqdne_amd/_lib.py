@@ -213,6 +213,9 @@ _PROTOS = {
     "tq_stem_head_bwd_workspace": (SZ, []),
     "tq_stem_conv_bwd_weight_ws": (I, [VP] * 4 + [I] * 5 + [VP, SZ, VP]),
     "tq_head_conv_bwd_ws": (I, [VP] * 10 + [I] * 5 + [VP, SZ, VP]),
+    "tq_boundary_max_channels": (I, []),
+    "tq_nct_to_btc": (I, [VP] * 4 + [I] * 5 + [VP]),
+    "tq_btc_to_nct": (I, [VP] * 5 + [I] * 5 + [VP]),
 }
 
 def lib_path() -> str:

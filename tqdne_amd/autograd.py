@@ -182,7 +182,7 @@ class _DenoiseFn(th.autograd.Function):
         if ctx.want_dx:
             c_in, c_skip = ctx.in_skip[0], ctx.in_skip[1]
             dx = eng._bwd.last_dx   # (already times c_in where the stem load applied it; the concatenated input was pre-scaled)
-            if ctx.concat:
+            if ctx.concat and not eng.wide_stem:   # (a wide stem's tq_btc_to_nct selected the sample's channels and applied c_in)
                 dx = dx[:, :ctx.shape[1]] * c_in[:, None, None]
             dx = dx + c_skip[:, None, None] * gout
         return (None, dx, None, None, None) + tuple(grads)

@@ -27,7 +27,7 @@ class _ICTLossFn(torch.autograd.Function):
     """loss = mean(w_t * (sqrt((f(x + s_{t+1} eps, s_{t+1}) - sg[f(x + s_t eps, s_t)])^2 + c^2) - c)),  c = 0.00054 sqrt(dim)."""
 
     @staticmethod
-    def forward(ctx, module, sample, sigmas, timesteps, epsilon, cond, *params):
+    def forward(ctx, module, sample, sigmas, timesteps, epsilon, cond, cond_sample, *params):
         engine.require_device(sample)
         B, nd = sample.shape[0], sample.dim()
         seed = rng.next_dropout_seed()  # one seed: teacher = student masks
@@ -47,8 +47,9 @@ class _ICTLossFn(torch.autograd.Function):
         # the two noised copies (consistency_model.py:150-160), teacher first (no gradient, same dropout masks as the student)
         check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(t_sig), _p(bufs["xt"]), B, per, stream), "noise (teacher)")
         check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(s_sig), _p(bufs["xs"]), B, per, stream), "noise (student)")
-        bufs["target"].copy_(module._forward_static(bufs["xt"], t_sig, cond, train=train, dropout_seed=seed))
-        pred = module._forward_static(bufs["xs"], s_sig, cond, train=train, dropout_seed=seed)
+        # (a conditioning signal is concatenated behind both noised copies, consistency_model.py:63-66,111-118; it gets no gradient)
+        bufs["target"].copy_(module._forward_static(bufs["xt"], t_sig, cond, train=train, dropout_seed=seed, cond_sample=cond_sample))
+        pred = module._forward_static(bufs["xs"], s_sig, cond, train=train, dropout_seed=seed, cond_sample=cond_sample)
         c = 0.00054 * float(np.sqrt(np.prod(sample.shape[2:])))
         w = (1 / (sigmas[1:] - sigmas[:-1]))[timesteps].float().contiguous()   # (B,) weights: indexing glue, as the schedule
         check(lib.tq_pseudo_huber_loss(_p(pred), _p(bufs["target"]), _p(w), c, _p(bufs["loss"]), _p(bufs["dpred"]), B, per, stream),
@@ -67,7 +68,7 @@ class _ICTLossFn(torch.autograd.Function):
             raise RuntimeError("another forward of the same shape ran between this loss and its backward: the execution plan's static "
                                "buffers no longer hold its activations")
         grads = eng.backward(ctx.dpred, gloss)
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 7 + tuple(grads)
 
 
 class LithningConsistencyModel(LightningModule):  # (sic) the reference's class name
@@ -82,7 +83,9 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         self.lognormal_mean, self.lognormal_std, self.lr = lognormal_mean, lognormal_std, lr
         self._scal = scratch_cache()
 
-    def _forward_static(self, sample, sigma, cond, lane=0, train=False, dropout_seed=0, infer=False):
+    def _forward_static(self, sample, sigma, cond, lane=0, train=False, dropout_seed=0, infer=False, cond_sample=None):
+        """``cond_sample``: conditioning signal concatenated on the channel axis behind the sample (consistency_model.py:63-66): the
+        network sees the concatenation, the skip term the sample alone."""
         lib = _lib.load()
         B, _, T = sample.shape
         dev = sample.device
@@ -95,15 +98,26 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         check(lib.tq_cm_scalars(_p(sigma), 1, float(self.sigma_data), float(self.sigma_min), _p(sc[0]), _p(sc[1]), B, stream),
               "cm scalars")
         eng = self.net._engine(B, T, dev, lane)
-        return eng.forward(sample, sigma, cond, in_scale=None, c_out=sc[0], c_skip=sc[1], skip_src=sample, train=train,
+        x_in = sample
+        if cond_sample is not None and eng.wide_stem:   # (the stem's layout kernel concatenates the conditioning signal itself)
+            return eng.forward(sample, sigma, cond, in_scale=None, c_out=sc[0], c_skip=sc[1], skip_src=sample, train=train,
+                               dropout_seed=dropout_seed, infer=infer, cond_x=cond_sample)
+        if cond_sample is not None:
+            C1 = cond_sample.shape[1]
+            kx = ("x_in", B, sample.shape[1] + C1, T, str(dev), lane)
+            x_in = self._scal.get(kx)
+            if x_in is None:
+                x_in = self._scal[kx] = torch.empty(B, sample.shape[1] + C1, T, device=dev)
+            check(lib.tq_concat_scale(_p(sample), None, _p(cond_sample), _p(x_in), B, sample.shape[1], C1, T, stream), "concat")
+        return eng.forward(x_in, sigma, cond, in_scale=None, c_out=sc[0], c_skip=sc[1], skip_src=sample, train=train,
                            dropout_seed=dropout_seed, infer=infer)
 
     def forward(self, sample, sigma, cond_sample=None, cond=None, _check_range=True):
         """consistency_model.py:63-79."""
         engine.require_device(sample)
-        if cond_sample is not None:
-            raise NotImplementedError("cond_sample concatenation is not used by any 1-D consistency config")
         sample, sigma = sample.contiguous(), sigma.contiguous().float()
+        if cond_sample is not None:
+            cond_sample = cond_sample.contiguous().float()
         B = sample.shape[0]
         lanes = 1  # one forward cannot amortise 4x the launches (measured 8.3 vs 6.5 ms at B = 64); kept for TQDNE experiments
         if os.environ.get("TQDNE_CM_LANES"):
@@ -112,9 +126,9 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
             lanes = 1
         if lanes < 2:
             infer = not torch.is_grad_enabled()
-            y = self._forward_static(sample, sigma, cond, infer=infer).clone()
+            y = self._forward_static(sample, sigma, cond, infer=infer, cond_sample=cond_sample).clone()
             if infer and _check_range and self.net._engine(B, sample.shape[2], sample.device, 0).check_range():
-                y = self._forward_static(sample, sigma, cond, infer=infer).clone()  # (the plan is on bf16x3 now)
+                y = self._forward_static(sample, sigma, cond, infer=infer, cond_sample=cond_sample).clone()  # (the plan is on bf16x3 now)
             return y
         # independent samples: sub-batches on separate HIP streams run out of phase (see LightningEDM.sample_deterministically)
         dev = sample.device
@@ -128,7 +142,8 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
             with torch.cuda.stream(st):
                 sl = slice(i * h, (i + 1) * h)
                 y = self._forward_static(sample[sl].contiguous(), sigma[sl].contiguous(),
-                                         None if cond is None else cond[sl].contiguous(), lane=engine.CONCURRENT_LANE0 + i, infer=True)
+                                         None if cond is None else cond[sl].contiguous(), lane=engine.CONCURRENT_LANE0 + i, infer=True,
+                                         cond_sample=None if cond_sample is None else cond_sample[sl].contiguous())
                 out[sl].copy_(y)
         for i in range(1, lanes):
             main.wait_stream(self._side_stream(dev, i))
@@ -180,8 +195,7 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         dropout masks as the student), student at sigma_{t+1}, weighted pseudo-Huber distance.  Both UNet passes and the
         backward are HIP; the schedule, the (B,)-sized draws and the loss on the (B, C, T) outputs are torch glue."""
         sample = batch["signal"]
-        if "cond_signal" in batch:
-            raise NotImplementedError("cond_signal is not used by any 1-D consistency config")
+        cond_sample = batch["cond_signal"].detach().contiguous().float() if "cond_signal" in batch else None
         cond = batch["cond"] if "cond" in batch else None
         sigmas = self._schedule()
         z = lambda s_: torch.erf((torch.log(s_) - self.lognormal_mean) / (self.lognormal_std * np.sqrt(2)))
@@ -189,7 +203,7 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         pdf = pdf / pdf.sum()
         timesteps = torch.multinomial(pdf, sample.shape[0], replacement=True)
         epsilon = torch.randn_like(sample)
-        return _ICTLossFn.apply(self, sample.contiguous(), sigmas, timesteps, epsilon, cond, *self.net.parameters())
+        return _ICTLossFn.apply(self, sample.contiguous(), sigmas, timesteps, epsilon, cond, cond_sample, *self.net.parameters())
 
     def training_step(self, batch, batch_idx: int):
         loss = self.step(batch)

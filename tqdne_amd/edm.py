@@ -139,6 +139,11 @@ class LightningEDM(LightningModule):
         stream = th.cuda.current_stream(dev).cuda_stream
         check(lib.tq_edm_scalars(_p(sigma), sigma_stride, float(self.edm.sigma_data), _p(sc[0]), _p(sc[1]), _p(sc[2]),
                                  _p(sc[3]), _p(sc[4]), B, stream), "edm scalars")
+        if cond_sample is not None and self.unet._engine(B, T, dev, self._lane).wide_stem:
+            # more than 16 input channels: the stem's layout kernel scales the sample and concatenates the conditioning signal itself
+            eng = self.unet._engine(B, T, dev, self._lane)
+            return eng.forward(sample, sc[3], cond, in_scale=sc[0], c_out=sc[1], c_skip=sc[2], skip_src=sample, train=train,
+                               dropout_seed=dropout_seed, infer=infer, cond_x=cond_sample.contiguous().float())
         if cond_sample is not None:
             C1 = cond_sample.shape[1]
             key = ("cat", B, sample.shape[1], C1, T, str(dev), self._lane)

@@ -197,10 +197,10 @@ class PackedStore:
         self.pack_stream = None
         self.users = {}         # stream handle -> event recorded behind that stream's most recent forward
 
-    def entry(self, key, shape, dtype=torch.uint8):
+    def entry(self, key, shape, dtype=torch.uint8, zero=False):
         e = self.entries.get(key)
         if e is None:
-            e = {"buf": torch.empty(shape, dtype=dtype, device=self.dev), "ver": None}
+            e = {"buf": (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.dev), "ver": None}
             self.entries[key] = e
         assert tuple(e["buf"].shape) == (tuple(shape) if isinstance(shape, (tuple, list)) else (shape,)), key
         return e
@@ -217,12 +217,22 @@ def get_store(model, device) -> PackedStore:
 class ConvSite:
     """One convolution's weights: torch parameter + packed bf16 hi/lo MFMA fragments (a buffer of the model's PackedStore)."""
 
-    __slots__ = ("weight", "bias", "packed", "packed_t", "pack_mode_t", "C_out", "C_in", "K", "version", "name", "pack_mode", "entry", "tail")
+    __slots__ = ("weight", "bias", "packed", "packed_t", "pack_mode_t", "C_out", "C_in", "K", "version", "name", "pack_mode", "entry", "tail",
+                 "w_co", "w_ci", "bias_pad")
 
-    def __init__(self, name, weight, bias, device, lib, packed=None, tail_bytes=0, store=None):
+    def __init__(self, name, weight, bias, device, lib, packed=None, tail_bytes=0, store=None, pad_cin=None, pad_cout=None):
         self.name = name
         self.weight, self.bias = weight, bias
-        self.C_out, self.C_in, self.K = weight.shape
+        self.w_co, self.w_ci, self.K = weight.shape
+        # C_out / C_in: what the kernels see.  A stem / head of 17 ... 64 signal channels runs padded to the 32-channel granule
+        # (pad_cin / pad_cout); the packers are given the real (w_co, w_ci) and zero-fill the missing rows -- the fragment geometry of
+        # the real and the padded shape is the same in every pack mode (ceil(c / 32) chunks, rows rounded up to the 32-row tile)
+        self.C_out, self.C_in = pad_cout or self.w_co, pad_cin or self.w_ci
+        assert self.C_out >= self.w_co and self.C_in >= self.w_ci
+        self.bias_pad = None   # (C_out,) copy of the bias whose entries >= w_co are zero (padded output channels only)
+        if self.C_out != self.w_co and bias is not None:
+            self.bias_pad = (store.entry("bias:" + name, (self.C_out,), torch.float32, zero=True)["buf"] if store is not None
+                             else torch.zeros(self.C_out, dtype=torch.float32, device=device))
         nbytes = lib.tq_conv_weight_pack_bytes(self.C_out, self.C_in, self.K, 0)
         # tail_bytes: room for a second conv's fragments right behind this one's (fused skip conv, tq_conv1d_fwd_skip)
         self.entry = None      # store entry owning `packed` (None: a tail view of another site's buffer, or a private buffer)
@@ -261,6 +271,19 @@ def _check_stem_limits(C_in: int, C_out: int, k: int, name: str = "input_blocks.
         raise NotImplementedError(
             f"input conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP stem kernels take C_in <= 16, C_out a multiple of 32 up to "
             "1024 (or a power of two from 4) and k in (1, 3, 5)")
+
+
+NARROW_SIGNAL_CHANNELS = 16   # most signal channels of the dedicated stem / head kernels (what their *_lds_bytes queries answer for)
+
+
+def _check_boundary_limits(what: str, name: str, channels: int, k: int):
+    """A stem / head beyond the dedicated kernels' 16 signal channels: tq_nct_to_btc / tq_btc_to_nct around a generic conv site."""
+    most = _lib.load().tq_boundary_max_channels()
+    if channels > most or k not in (1, 3, 5):
+        raise NotImplementedError(
+            f"{what} {name}: {channels} signal channels, k = {k}: the HIP path takes up to {most} signal channels at either end (up to "
+            f"{NARROW_SIGNAL_CHANNELS} in the dedicated stem / head kernels, {NARROW_SIGNAL_CHANNELS + 1} ... {most} through the "
+            "channels-last boundary kernels and the MFMA convs) and k in (1, 3, 5)")
 
 
 def _check_head_bwd_limits(C_in: int, C_out: int, k: int, name: str = "out.2"):
@@ -384,8 +407,8 @@ class UNetEngine:
         self.acts.append(a)
         return a
 
-    def _site(self, name: str, conv: torch.nn.Module) -> ConvSite:
-        s = ConvSite(name, conv.weight, conv.bias, self.dev, self.lib, store=self.store)
+    def _site(self, name: str, conv: torch.nn.Module, pad_cin=None, pad_cout=None) -> ConvSite:
+        s = ConvSite(name, conv.weight, conv.bias, self.dev, self.lib, store=self.store, pad_cin=pad_cin, pad_cout=pad_cout)
         self.conv_sites.append(s)
         return s
 
@@ -545,8 +568,8 @@ class UNetEngine:
         elif launch:
             op = (self.lib.tq_conv1d_fwd, (
                 C.byref(d), _p(s0.buf), _p(s1.buf) if s1 else None, _p(gn[0]) if gn else None, _p(gn[1]) if gn else None,
-                _p(site.packed), _p(site.bias), emb_ptr, _p(res.buf) if res else None, _p(out.buf), _p(out.stats)),
-                "conv:" + site.name, flops)
+                _p(site.packed), _p(site.bias_pad if site.bias_pad is not None else site.bias), emb_ptr, _p(res.buf) if res else None,
+                _p(out.buf), _p(out.stats)), "conv:" + site.name, flops)
             infer_op = None
             # (two-phase form: its 2 * ceil(T_in / 128) statistics slots must be the tensor's ceil(2 T_in / 128))
             if (upsample and site.K == 5 and (T_in % STAT_SLOT == 0 or T_in % STAT_SLOT > STAT_SLOT // 2) and site.C_out % 32 == 0 and gn is None and res is None
@@ -633,8 +656,7 @@ class UNetEngine:
 
         # stem (dynamic args: x, in_scale) -------------------------------------------------------
         stem = m.input_blocks[0][0]
-        _check_stem_limits(m.in_channels, stem.out_channels, stem.kernel_size[0])
-        self.stem_out = self._act(stem.out_channels, T, True)
+        self._stem(stem, m.in_channels, T, "input_blocks.0.0")
         hs = [self.stem_out]
         h = self.stem_out
         self._site_counter = 0
@@ -669,10 +691,48 @@ class UNetEngine:
             skip = hs.pop()
             h = run_layers(blk, (h, skip), f"output_blocks.{i}")
         self.final = h
-        _check_head_limits(h.C, m.out[2].out_channels, m.out[2].kernel_size[0])
+        self.wide_head = m.out[2].out_channels > NARROW_SIGNAL_CHANNELS
+        if not self.wide_head:
+            _check_head_limits(h.C, m.out[2].out_channels, m.out[2].kernel_size[0])
         self.head_gn = self._gn([h], m.out[0])
+        if self.wide_head:
+            self._wide_head(h, m.out[2], "out.2", self.head_gn)
         self.out_nct = self._empty(B, m.out_channels, T)
         assert getattr(self, "_pending_gn", None) is None, "a deferred GroupNorm finalisation was never placed"
+
+    def _stem(self, stem, cin: int, T: int, name: str):
+        """The first conv.  Up to 16 signal channels: the dedicated kernel (tq_stem_conv_fwd, launched by ``forward`` with the dynamic
+        arguments x / in_scale).  17 ... tq_boundary_max_channels(): tq_nct_to_btc (same dynamic arguments) fills a static channels-last
+        buffer padded to the 32-channel granule, and the conv is an ordinary site of the plan -- its first launch -- with the output's
+        GroupNorm statistics and the range guard."""
+        self.wide_stem = cin > NARROW_SIGNAL_CHANNELS
+        if not self.wide_stem:
+            _check_stem_limits(cin, stem.out_channels, stem.kernel_size[0], name)
+            self.stem_out = self._act(stem.out_channels, T, True)
+            return
+        _check_boundary_limits("input conv", name, cin, stem.kernel_size[0])
+        self.x_btc = self._act((cin + 31) // 32 * 32, T, stats=False)
+        self.stem_out = self._conv([self.x_btc], self._site(name, stem, pad_cin=self.x_btc.C), stats=True)
+        self.stem_rec = self.last_rec
+
+    def _wide_head(self, h: Act, conv, name: str, gn):
+        """The last conv with 17 ... tq_boundary_max_channels() output channels: an ordinary site (GroupNorm + SiLU prologue where the
+        model has one) whose output channels are padded to the 32-channel granule with zero weight rows and bias entries;
+        ``forward`` follows it with tq_btc_to_nct and the dynamic epilogue arguments."""
+        _check_boundary_limits("output conv", name, conv.out_channels, conv.kernel_size[0])
+        site = self._site(name, conv, pad_cout=(conv.out_channels + 31) // 32 * 32)
+        self.head_btc = self._conv([h], site, gn=gn, silu=gn is not None, stats=False)
+        self.head_rec = self.last_rec
+
+    def _run_stem(self, x, in_scale, stem, cin, stream, what, cond_x=None):
+        if self.wide_stem:
+            c1 = 0 if cond_x is None else cond_x.shape[1]
+            check(self.lib.tq_nct_to_btc(_p(x), _p(in_scale), _p(cond_x), _p(self.x_btc.buf), self.B, cin - c1, c1, self.T, self.x_btc.C,
+                                         stream), what + " (nct_to_btc)")
+        else:
+            check(self.lib.tq_stem_conv_fwd(_p(x), _p(in_scale), _p(stem.weight), _p(stem.bias), _p(self.stem_out.buf),
+                                            _p(self.stem_out.stats), self.B, cin, self.T, stem.out_channels, stem.kernel_size[0],
+                                            stream), what)
 
     def _res_block(self, x, rb, name: str) -> Act:
         srcs = list(x) if isinstance(x, tuple) else [x]
@@ -862,6 +922,8 @@ class UNetEngine:
             if st.entry is None:
                 continue  # tail of a pair: packed with its head
             ver = (id(st.weight), st.weight._version, st.pack_mode) + ((id(st.tail.weight), st.tail.weight._version) if st.tail else ())
+            if st.bias_pad is not None:
+                ver += (id(st.bias), st.bias._version)
             if st.entry["ver"] != ver:
                 sites.append((st, ver))
         polys = []
@@ -888,6 +950,8 @@ class UNetEngine:
         v = 0
         for st in self.conv_sites:
             v += st.weight._version
+            if st.bias_pad is not None:
+                v += st.bias._version
         for rb in self.res_blocks:
             if hasattr(rb, "emb_layers"):
                 v += rb.emb_layers[1].weight._version + rb.emb_layers[1].bias._version
@@ -907,10 +971,12 @@ class UNetEngine:
                         cur.wait_event(ev)
             jobs = []
             for st, ver in sites:
-                jobs.append((st.weight.data_ptr(), st.packed.data_ptr(), st.C_out, st.C_in, st.K, st.pack_mode))
+                jobs.append((st.weight.data_ptr(), st.packed.data_ptr(), st.w_co, st.w_ci, st.K, st.pack_mode))
+                if st.bias_pad is not None:   # (entries >= w_co stay zero: the buffer was zero-filled when it was made)
+                    jobs.append((st.bias.data_ptr(), st.bias_pad.data_ptr(), st.w_co, 0, 0, 4))
                 if st.tail is not None:
                     t = st.tail
-                    jobs.append((t.weight.data_ptr(), t.packed.data_ptr(), t.C_out, t.C_in, t.K, t.pack_mode))
+                    jobs.append((t.weight.data_ptr(), t.packed.data_ptr(), t.w_co, t.w_ci, t.K, t.pack_mode))
                 st.entry["ver"] = ver
             if emb is not None:   # gather of the ResBlocks' embedding projections into the concatenated (emb_total, E) buffers
                 for rb in self.res_blocks:
@@ -958,18 +1024,28 @@ class UNetEngine:
         v = (sum(s.weight._version for s in self.dgrad_sites), sum(s.pack_mode_t for s in self.dgrad_sites))
         if v == self._wt_version:
             return
-        pack_batch(self.lib, self.dev, [(s.weight.data_ptr(), s.packed_t.data_ptr(), s.C_out, s.C_in, s.K, s.pack_mode_t)
+        pack_batch(self.lib, self.dev, [(s.weight.data_ptr(), s.packed_t.data_ptr(), s.w_co, s.w_ci, s.K, s.pack_mode_t)
                                         for s in self.dgrad_sites], stream, torch.cuda.is_current_stream_capturing())
         self._wt_version = v
 
     # ------------------------------------------------------------------ run
     def forward(self, x, timesteps, cond=None, *, in_scale=None, c_out=None, c_skip=None, skip_src=None,
-                train: bool = False, dropout_seed: int = 0, infer: bool = False):
+                train: bool = False, dropout_seed: int = 0, infer: bool = False, cond_x=None):
         """Run the UNet.  Returns the static (B, C_out, T) output buffer (overwritten by the next call).
-        ``infer``: no backward will follow this forward -- launches may skip what only the backward reads (``ops_infer``)."""
+        ``infer``: no backward will follow this forward -- launches may skip what only the backward reads (``ops_infer``).
+        ``cond_x`` (plans with a wide stem only): a conditioning signal (B, C1, T) that the stem's tq_nct_to_btc concatenates, unscaled,
+        behind ``x`` (B, in_channels - C1, T) -- the concatenation is never materialised in NCW."""
         m, lib, B, T = self.m, self.lib, self.B, self.T
-        if tuple(x.shape) != (B, m.in_channels, T):
-            raise ValueError(f"plan was built for {(B, m.in_channels, T)}, got {tuple(x.shape)}")
+        c1 = 0
+        if cond_x is not None:
+            if not self.wide_stem:
+                raise ValueError("cond_x needs a plan with a wide stem (more than 16 input channels)")
+            cond_x = cond_x.contiguous()
+            c1 = cond_x.shape[1]
+            if tuple(cond_x.shape) != (B, c1, T):
+                raise ValueError(f"plan was built for {(B, c1, T)} conditioning signals, got {tuple(cond_x.shape)}")
+        if tuple(x.shape) != (B, m.in_channels - c1, T):
+            raise ValueError(f"plan was built for {(B, m.in_channels - c1, T)}, got {tuple(x.shape)}")
         x = x.contiguous()
         timesteps = timesteps.contiguous().float()
         if timesteps.shape != (B,):
@@ -1008,13 +1084,14 @@ class UNetEngine:
             trace.append(("embed", 2 * B * self.E * (self.emb_total + 2 * self.E), 4 * (self.emb_total * self.E + B * self.emb_total), e0, e1))
             e0 = e1
         stem = m.input_blocks[0][0]
-        check(lib.tq_stem_conv_fwd(_p(x), _p(in_scale), _p(stem.weight), _p(stem.bias), _p(self.stem_out.buf),
-                                   _p(self.stem_out.stats), B, m.in_channels, T, stem.out_channels, stem.kernel_size[0],
-                                   stream), "stem conv")
+        self._run_stem(x, in_scale, stem, m.in_channels, stream, "stem conv", cond_x)
         if ev:
             e1 = ev()
-            trace.append(("stem", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
-                          4 * B * T * (m.in_channels + stem.out_channels), e0, e1))
+            if self.wide_stem:
+                trace.append(("nct_to_btc:stem", 0, 4 * B * T * (m.in_channels + self.x_btc.C), e0, e1))
+            else:
+                trace.append(("stem", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
+                              4 * B * T * (m.in_channels + stem.out_channels), e0, e1))
         probe = self._probe
         ops = self.ops_infer if (infer and not train) else self.ops
         if trace is not None:
@@ -1043,16 +1120,22 @@ class UNetEngine:
                 if rc:
                     check(rc, what)
         self._fwd_count = getattr(self, "_fwd_count", 0) + 1
-        self._last = dict(x=x, in_scale=in_scale, c_out=c_out, timesteps=timesteps, cond=cond, train=train,
+        self._last = dict(x=x, in_scale=in_scale, c_out=c_out, timesteps=timesteps, cond=cond, train=train, c0=m.in_channels - c1,
                           dropout_p=p, dropout_seed=dropout_seed, infer=infer and not train, block_kv=self._block_kv)
         head = m.out[2]
         e0 = ev() if ev else None
-        check(lib.tq_head_conv_fwd(_p(self.final.buf), _p(self.head_gn[0]), _p(self.head_gn[1]), _p(head.weight),
-                                   _p(head.bias), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
-                                   self.final.C, m.out_channels, head.kernel_size[0], stream), "head conv")
-        if ev:
-            trace.append(("head", 2 * B * T * self.final.C * m.out_channels * head.kernel_size[0],
-                          4 * B * T * (self.final.C + 2 * m.out_channels), e0, ev()))
+        if self.wide_head:   # (the conv itself was the plan's last launch)
+            check(lib.tq_btc_to_nct(_p(self.head_btc.buf), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
+                                    self.head_btc.C, 0, m.out_channels, stream), "head epilogue (btc_to_nct)")
+            if ev:
+                trace.append(("btc_to_nct:head", 0, 4 * B * T * (self.head_btc.C + 2 * m.out_channels), e0, ev()))
+        else:
+            check(lib.tq_head_conv_fwd(_p(self.final.buf), _p(self.head_gn[0]), _p(self.head_gn[1]), _p(head.weight),
+                                       _p(head.bias), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
+                                       self.final.C, m.out_channels, head.kernel_size[0], stream), "head conv")
+            if ev:
+                trace.append(("head", 2 * B * T * self.final.C * m.out_channels * head.kernel_size[0],
+                              4 * B * T * (self.final.C + 2 * m.out_channels), e0, ev()))
         if train:
             self._range_poll(False)
         self._mark_use(stream)
@@ -1090,10 +1173,7 @@ class SeqEngine(UNetEngine):
         self.res_blocks, self.emb_offsets, self.emb_total = [], {}, 0
         self._site_counter = 0
         stem = m.input_layer
-        if stem.in_channels > 16:
-            raise NotImplementedError("input layer with more than 16 channels")
-        _check_stem_limits(stem.in_channels, stem.out_channels, stem.kernel_size[0], "input_layer")
-        self.stem_out = self._act(stem.out_channels, T, True)
+        self._stem(stem, stem.in_channels, T, "input_layer")
         h = self.stem_out
         blocks = getattr(m, m.blocks_attr)
         for li, layer in enumerate(blocks):
@@ -1143,11 +1223,13 @@ class SeqEngine(UNetEngine):
         trace = None if torch.cuda.is_current_stream_capturing() else self._trace   # (measurement only: HIP events around every launch)
         ev = _recorded_event if trace is not None else None
         e0 = ev() if ev else None
-        check(lib.tq_stem_conv_fwd(_p(x), None, _p(stem.weight), _p(stem.bias), _p(self.stem_out.buf), _p(self.stem_out.stats), B,
-                                   m.in_channels, T, stem.out_channels, stem.kernel_size[0], stream), "input layer")
+        self._run_stem(x, None, stem, m.in_channels, stream, "input layer")
         if ev:
-            trace.append(("input layer", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
-                          4 * B * T * (m.in_channels + stem.out_channels), e0, ev()))
+            if self.wide_stem:
+                trace.append(("nct_to_btc:input layer", 0, 4 * B * T * (m.in_channels + self.x_btc.C), e0, ev()))
+            else:
+                trace.append(("input layer", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
+                              4 * B * T * (m.in_channels + stem.out_channels), e0, ev()))
         for i, (fn, args, what, fl) in enumerate(self.ops):
             a = ev() if ev else None
             rc = fn(*args, stream)

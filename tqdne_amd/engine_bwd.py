@@ -44,6 +44,13 @@ DGRAD_MX6_C64 = __import__("os").environ.get("TQDNE_DGRAD_MX6_C64", "0") == "1" 
 N_AMAX = 160   # blocks for max|dy| (one per gradient tensor that feeds a data gradient), kept in the tail of the flat buffer
 
 
+def _copy_floats(dst, src, n, stream):
+    """a plan op: n floats device to device on ``stream``"""
+    from .engine import _lib_copy_floats
+    _lib_copy_floats(dst, src, n, stream)
+    return 0
+
+
 def _nslots(T):
     return (T + STAT_SLOT - 1) // STAT_SLOT
 
@@ -218,11 +225,12 @@ class BackwardPlan:
         return self.gview[id(param)]
 
     # ------------------------------------------------------------------ emitters
-    def _wgrad(self, rec, dy, bias_colsum=True, colsum=None):
+    def _wgrad(self, rec, dy, bias_colsum=True, colsum=None, dw=None):
         """weight gradient of one conv, behind the column sums of dy that the block needs anyway (bias gradients, the per-sample
         gradient of the broadcast time embedding; ``_colsum_pass``): ``colsum`` = (per-sample destination address | None, its row
         stride, bias gradient tensor | None, second bias gradient tensor | None); ``bias_colsum``: default = this conv's own bias.
-        (The sums inside the weight-gradient launch, tq_conv1d_bwd_weight_colsum's optional arguments, measured slower: not used.)"""
+        (The sums inside the weight-gradient launch, tq_conv1d_bwd_weight_colsum's optional arguments, measured slower: not used.)
+        ``dw``: destination (C_out, C_in, K) of the site's PADDED geometry where that differs from the parameter's (wide head)."""
         lib, site = self.lib, rec.site
         need = lib.tq_conv1d_bwd_weight_workspace(C.byref(rec.desc))
         self.ws_bytes = max(getattr(self, "ws_bytes", 0), need)
@@ -237,7 +245,8 @@ class BackwardPlan:
         self.op_flops[len(self.ops)] = 2 * site.C_in * site.C_out * site.K * rec.desc.T_out * self.B
         self.ops.append([lib.tq_conv1d_bwd_weight_colsum, [C.byref(rec.desc), _p(dy), _p(s0.buf), _p(s1.buf) if s1 else None,
                                                            _p(rec.gn[0]) if rec.gn else None, _p(rec.gn[1]) if rec.gn else None,
-                                                           _p(self.g(site.weight)), None, 0, None, 0, None, None], "wgrad:" + site.name])
+                                                           _p(dw) if dw is not None else _p(self.g(site.weight)), None, 0, None, 0, None,
+                                                           None], "wgrad:" + site.name])
 
     def _colsum_pass(self, dy, T_dy, C_dy, bc, stride, c1, c2, name):
         """column sums (bias / per-sample embedding gradients) and max|dy| of the gradient tensor ``dy`` (B, T_dy, C_dy): inside the
@@ -354,16 +363,21 @@ class BackwardPlan:
         final = e.final
         head = m.out[2]
         from .engine import _check_head_bwd_limits
-        _check_head_bwd_limits(final.C, m.out_channels, head.kernel_size[0])
+        self.wide_head = bool(getattr(e, "wide_head", False))
+        if not self.wide_head:
+            _check_head_bwd_limits(final.C, m.out_channels, head.kernel_size[0])
         Gh = self.scratch("G", final.T, final.C)
-        gst = self._empty(B, _nslots(final.T), final.C, 2)
         # (scratch for the two-stage sums of the head / stem weight gradients: one buffer each, see tq_stem_head_bwd_workspace)
         nws = lib.tq_stem_head_bwd_workspace()
         self._ws_head = torch.empty(nws, dtype=torch.uint8, device=self.dev)
         self._ws_stem = torch.empty(nws, dtype=torch.uint8, device=self.dev)
-        self.head_op = [lib.tq_head_conv_bwd_ws, [None, None, _p(final.buf), _p(e.head_gn[0]), _p(e.head_gn[1]), _p(head.weight), _p(Gh),
-                                                  _p(gst), _p(self.g(head.weight)), _p(self.g(head.bias)), B, final.T, final.C,
-                                                  m.out_channels, head.kernel_size[0], _p(self._ws_head), nws], "head bwd"]
+        if self.wide_head:
+            gst = self._wide_head_bwd(e.head_rec, head, final, Gh, m.out_channels)
+        else:
+            gst = self._empty(B, _nslots(final.T), final.C, 2)
+            self.head_op = [lib.tq_head_conv_bwd_ws, [None, None, _p(final.buf), _p(e.head_gn[0]), _p(e.head_gn[1]), _p(head.weight), _p(Gh),
+                                                      _p(gst), _p(self.g(head.weight)), _p(self.g(head.bias)), B, final.T, final.C,
+                                                      m.out_channels, head.kernel_size[0], _p(self._ws_head), nws], "head bwd"]
         coef = self._gn_bwd(gst, e.head_gn, m.out[0], final.T, final.C)
         self._gn_apply(Gh, final, coef, final.C, 0)
         # ---- blocks, reversed
@@ -378,17 +392,24 @@ class BackwardPlan:
         self._ready[id(stem.weight)] = self.END  # (run after the sweep, not from self.ops)
         # wide stems (the latent UNet's 16 input channels: 64 x 16 x 5 weights exceed the dedicated kernel's register budget)
         # are differentiated as a generic fused conv over a (B, T, 32) channels-last copy of the pre-scaled input
-        self.stem_generic = stem.out_channels * m.in_channels * stem.kernel_size[0] > 2048
+        # ... and stems of more than 16 signal channels, whose forward already is that generic conv: the weight gradient reads the
+        # padded channels-last input the forward's tq_nct_to_btc wrote (no copy)
+        self.wide_stem = bool(getattr(e, "wide_stem", False))
+        self.stem_cp = e.x_btc.C if self.wide_stem else 32
+        self.stem_generic = self.wide_stem or stem.out_channels * m.in_channels * stem.kernel_size[0] > 2048
         if self.stem_generic:
             from ._lib import TqConvDesc
-            K = stem.kernel_size[0]
-            self.stem_x_btc = self._empty(B, so.T, 32)
-            self.stem_x_btc.zero_()
+            K, Cp = stem.kernel_size[0], self.stem_cp
+            if self.wide_stem:
+                self.stem_x_btc = e.x_btc.buf
+            else:
+                self.stem_x_btc = self._empty(B, so.T, Cp)
+                self.stem_x_btc.zero_()
             d = TqConvDesc()
-            d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, so.T, so.T, 32, 0, stem.out_channels
+            d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, so.T, so.T, Cp, 0, stem.out_channels
             d.ktaps, d.stride, d.pad, d.upsample, d.flags = K, 1, K // 2, 0, 0
             self._keep.append(d)
-            self.dw_stem32 = self._empty(stem.out_channels, 32, K)
+            self.dw_stem32 = self._empty(stem.out_channels, Cp, K)
             self.ws_bytes = max(getattr(self, "ws_bytes", 0), lib.tq_conv1d_bwd_weight_workspace(C.byref(d)))
             self._wgrad_ops.append(len(self.ops))
             self.ops.append([lib.tq_conv1d_bwd_weight, [C.byref(d), _p(so.grad), _p(self.stem_x_btc), None, None, None,
@@ -399,6 +420,26 @@ class BackwardPlan:
         for i in self._wgrad_ops:
             self.ops[i][1][7] = self.ws.data_ptr()
             self.ops[i][1][8] = self.ws.numel()
+
+    def _wide_head_bwd(self, rec, head, final, Gh, co):
+        """Backward of a head with 17 ... 64 output channels (engine._wide_head: a generic conv site padded to the 32-channel granule):
+        ``run`` writes dF = c_out[b] * dpred channels-last and zero-padded (tq_nct_to_btc, dynamic arguments); then the bias gradient
+        (column sums; the padding columns add zeros into the 64-float alignment gap behind the bias gradient), the weight gradient in
+        the padded geometry (its real rows are copied out after the sweep) and the data gradient chained through SiLU' / GroupNorm --
+        what tq_head_conv_bwd_ws leaves in Gh and the partial sums for the blocks upstream."""
+        site, Cp = rec.site, rec.site.C_out
+        self.dF = self._empty(self.B, final.T, Cp)
+        self.head_op = [self.lib.tq_nct_to_btc, [None, None, None, _p(self.dF), self.B, co, 0, final.T, Cp], "head dF (nct_to_btc)"]
+        if self.offs[id(head.bias)] % 64 or Cp > 64 or id(head.bias) not in self._swept_ids:
+            raise RuntimeError(f"{site.name}: the padded bias gradient ({Cp} column sums) needs the 64-float alignment gap behind the bias "
+                               "gradient in the flat buffer (_layout_gradients)")
+        self._colsum_pass(self.dF, final.T, Cp, None, 0, head.bias, None, site.name)
+        self.dw_head_pad = self._empty(Cp, site.C_in, site.K)
+        self._wgrad(rec, self.dF, bias_colsum=False, dw=self.dw_head_pad)
+        # the real rows are the first co * C_in * K floats of the padded result: copied out right behind the weight gradient (named like
+        # one: it follows it on the weight-gradient stream), so the head's gradients are final where the sweep begins, as a narrow head's
+        self.ops.append([_copy_floats, [_p(self.g(head.weight)), _p(self.dw_head_pad), head.weight.numel()], "wgrad:rows:" + site.name])
+        return self._dgrad(rec, self.dF, final.T, [Gh], accumulate=False)
 
     def _recompute(self, t):
         """use_checkpoint plans: re-issue the block's forward launches (same pre-bound calls as the forward plan's) so that its shared
@@ -552,13 +593,14 @@ class BackwardPlan:
         e, m, lib = self.e, self.m, self.lib
         stem, so = m.input_blocks[0][0], e.stem_out
         cin, K = stem.in_channels, stem.kernel_size[0]
-        if cin > 32:
-            raise NotImplementedError("input gradient for more than 32 input channels")
+        Cp = self.stem_cp
+        if cin > Cp:
+            raise NotImplementedError(f"input gradient for more than {Cp} input channels")
         if getattr(self, "dx_op", None) is None:
-            self.dx_btc = self._empty(self.B, so.T, 32)
+            self.dx_btc = self._empty(self.B, so.T, Cp)
             self.stem_packed_t = torch.empty(lib.tq_conv_weight_pack_bytes(stem.out_channels, cin, K, 1), dtype=torch.uint8, device=self.dev)
             bd = TqConvBwdDesc()
-            bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = self.B, so.T, stem.out_channels, 32, 0, K, 0
+            bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = self.B, so.T, stem.out_channels, Cp, 0, K, 0
             self._keep.append(bd)
             self.dx_op = [lib.tq_conv1d_bwd_data, [C.byref(bd), _p(so.grad), _p(self.stem_packed_t), None, None, None, None,
                                                    _p(self.dx_btc), None, None], "dgrad:stem"]
@@ -566,6 +608,14 @@ class BackwardPlan:
               "pack^T stem")
         fn, args, what = self.dx_op
         check(fn(*args, stream), what)
+        if self.wide_stem:
+            # layout change, the input scale and the choice of the channels that were the forward's ``x`` in one launch (a conditioning
+            # signal concatenated by the stem sits behind them and gets no gradient: the window starts at channel 0)
+            c0 = last.get("c0", cin)
+            dx = torch.empty(self.B, c0, so.T, dtype=torch.float32, device=self.dev)   # (a fresh tensor: autograd may keep it)
+            check(lib.tq_btc_to_nct(_p(self.dx_btc), _p(last["in_scale"]), None, None, _p(dx), self.B, so.T, Cp, 0, c0, stream),
+                  "input gradient (btc_to_nct)")
+            return dx
         dx = self.dx_btc[:, :, :cin].permute(0, 2, 1).contiguous()
         if last["in_scale"] is not None:
             dx.mul_(last["in_scale"][:, None, None])
@@ -613,7 +663,7 @@ class BackwardPlan:
         args[0], args[1] = dpred.data_ptr(), cs.data_ptr()
         check(fn(*args, stream), what)
         cin = m.in_channels
-        if self.stem_generic:
+        if self.stem_generic and not self.wide_stem:
             xs = last["x"] if last["in_scale"] is None else last["x"] * last["in_scale"][:, None, None]
             self.stem_x_btc[:, :, :cin].copy_(xs.permute(0, 2, 1))
         if self._trace is not None:
@@ -837,16 +887,22 @@ class SeqBackwardPlan(BackwardPlan):
         stem, so = m.input_layer, e.stem_out
         assert so.gw
         cin, K = stem.in_channels, stem.kernel_size[0]
-        self.x_btc = Act(self._empty(B, so.T, 32), None, 32, so.T)
-        self.x_btc.buf.zero_()
+        # (an input layer of more than 16 channels already ran as that generic conv: its padded channels-last input is the forward's)
+        self.wide_stem = bool(getattr(e, "wide_stem", False))
+        Cp = self.stem_cp = e.x_btc.C if self.wide_stem else 32
+        if self.wide_stem:
+            self.x_btc = e.x_btc
+        else:
+            self.x_btc = Act(self._empty(B, so.T, Cp), None, Cp, so.T)
+            self.x_btc.buf.zero_()
         site = ConvSite("input_layer", stem.weight, stem.bias, self.dev, lib)
-        site.C_in = 32  # descriptor / packed geometry see the padded input; pack kernels guard the real (C_out, cin, K) weight
+        site.C_in = Cp  # descriptor / packed geometry see the padded input; pack kernels guard the real (C_out, cin, K) weight
         d = TqConvDesc()
-        d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, so.T, so.T, 32, 0, stem.out_channels
+        d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, so.T, so.T, Cp, 0, stem.out_channels
         d.ktaps, d.stride, d.pad, d.upsample, d.flags = K, 1, K // 2, 0, 0
         self._keep.append(d)
         rec = ConvRec(site, d, [self.x_btc], None, so, 1, False, False, False)
-        self.dw_stem32 = self._empty(stem.out_channels, 32, K)
+        self.dw_stem32 = self._empty(stem.out_channels, Cp, K)
         need = lib.tq_conv1d_bwd_weight_workspace(C.byref(d))
         self.ws_bytes = max(getattr(self, "ws_bytes", 0), need)
         self._wgrad_ops.append(len(self.ops))
@@ -854,12 +910,12 @@ class SeqBackwardPlan(BackwardPlan):
                                                     _p(self.dw_stem32), None, 0], "wgrad:input_layer"])
         self.ops.append([lib.tq_colsum, [_p(so.grad), B, so.T, so.C, None, 0, _p(self.g(stem.bias)), None, None, None], "colsum:stem"])
         # d input (only run on request): transposed conv into a 32-channel channels-last buffer
-        self.dx_btc = self._empty(B, so.T, 32)
+        self.dx_btc = self._empty(B, so.T, Cp)
         n0 = len(self.ops)
         site.packed_t = torch.empty(lib.tq_conv_weight_pack_bytes(stem.out_channels, cin, K, 1), dtype=torch.uint8, device=self.dev)
         self.stem_site = site
         bd = TqConvBwdDesc()
-        bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = B, so.T, stem.out_channels, 32, 0, K, 0
+        bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = B, so.T, stem.out_channels, Cp, 0, K, 0
         self._keep.append(bd)
         self.dx_op = [lib.tq_conv1d_bwd_data, [C.byref(bd), _p(so.grad), _p(site.packed_t), None, None, None, None,
                                                _p(self.dx_btc), None, None], "dgrad:input_layer"]
@@ -889,7 +945,8 @@ class SeqBackwardPlan(BackwardPlan):
             else:
                 d.flags &= ~TQ_BWD_DROPOUT
         dout = dout.contiguous()
-        self.x_btc.buf[:, :, :cin].copy_(last["x"].permute(0, 2, 1))
+        if not self.wide_stem:
+            self.x_btc.buf[:, :, :cin].copy_(last["x"].permute(0, 2, 1))
         if self.head_op is not None:
             fn, args, what = self.head_op
             args[0] = dout.data_ptr()
@@ -905,7 +962,12 @@ class SeqBackwardPlan(BackwardPlan):
         if want_dx:
             fn, args, what = self.dx_op
             check(fn(*args, stream), what)
-            dx = self.dx_btc[:, :, :cin].permute(0, 2, 1).contiguous()
+            if self.wide_stem:
+                dx = torch.empty(self.B, cin, e.stem_out.T, dtype=torch.float32, device=self.dev)
+                check(lib.tq_btc_to_nct(_p(self.dx_btc), None, None, None, _p(dx), self.B, e.stem_out.T, self.stem_cp, 0, cin, stream),
+                      "input gradient (btc_to_nct)")
+            else:
+                dx = self.dx_btc[:, :, :cin].permute(0, 2, 1).contiguous()
         out = self.flat.clone() if clone else self.flat
         res = []
         for p_ in self.param_order:

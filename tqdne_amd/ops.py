@@ -25,29 +25,38 @@ def nslots(T):
     return (T + STAT_SLOT - 1) // STAT_SLOT
 
 
-def pack_conv_weight(w: torch.Tensor, mode: int = 0) -> torch.Tensor:
+def pack_conv_weight(w: torch.Tensor, mode: int = 0, geometry=None) -> torch.Tensor:
+    """``geometry`` = (C_out, C_in) of the launch where it is the weight's shape padded to the 32-channel granule (a stem / head of
+    17 ... 64 signal channels): the packers zero-fill the missing rows, and the fragment layout of both shapes is the same."""
     lib = _lib.load()
     co, ci, k = w.shape
-    out = torch.empty(lib.tq_conv_weight_pack_bytes(co, ci, k, mode), dtype=torch.uint8, device=w.device)
+    gco, gci = geometry or (co, ci)
+    assert gco >= co and gci >= ci and (gco - co) < 32 and (gci - ci) < 32
+    out = torch.empty(lib.tq_conv_weight_pack_bytes(gco, gci, k, mode), dtype=torch.uint8, device=w.device)
     check(lib.tq_pack_conv_weight(_p(w.contiguous()), co, ci, k, mode, _p(out), _stream(w.device)), "pack")
     return out
 
 
 def conv1d(x0, weight, bias=None, *, x1=None, gscale=None, gshift=None, silu=False, emb=None, residual=None,
            stride=1, upsample=False, stats=True, dropout_p=0.0, dropout_seed=0, dropout_site=0, skip=None, wfmt=None, t_tile=0,
-           gn_fold=None, wide_table=False, out=None):
+           gn_fold=None, wide_table=False, out=None, pad_cout=0):
     """x0/x1 (B, T, C) channels-last fp32; weight (C_out, C_in, K) torch layout.  Returns (y, stats|None).
     skip=(sx0, sx1|None, w_skip (C_out, Cs, 1), b_skip|None): fused 1x1 conv of the un-activated sx (tq_conv1d_fwd_skip).
     t_tile=32: the small tile (TqConvDesc.t_tile); the statistics then have one slot per 32 positions.
     gn_fold=(stats0, stats1|None, slot0, slot1, gamma, beta, mean_rstd|None): the launch folds its own GroupNorm (TqConvDesc.gn_fold) and
     WRITES the coefficients into ``gscale`` / ``gshift`` (pass empty (B, C_in) tensors) and ``mean_rstd``.
     wide_table=True: TQ_CONV_WIDE_TABLE -- the wide-table fp16 + MX-fp6 tile (what more than 1024 concatenated channels get) for a
-    narrower launch too; same bits.  ``out`` = (y, stats | None): caller-owned result buffers."""
+    narrower launch too; same bits.  ``out`` = (y, stats | None): caller-owned result buffers.
+    Padded ends (how the plans run a stem / head of 17 ... 64 signal channels): a weight with fewer input channels than x0 has (the
+    rest of x0 is zero padding), and ``pad_cout`` = the weight's output channels rounded up to a multiple of 32 (y gets that many
+    channels, the extra ones are zero; ``bias`` must then have ``pad_cout`` entries)."""
     lib = _lib.load()
     B, T_in, C0 = x0.shape
     C1 = 0 if x1 is None else x1.shape[2]
-    C_out, C_in, K = weight.shape
-    assert C_in == C0 + C1
+    w_co, C_in, K = weight.shape
+    C_out = pad_cout or w_co
+    assert C_in == C0 + C1 or (x1 is None and skip is None and 0 < C0 - C_in < 32)
+    assert not pad_cout or bias is None or bias.numel() == C_out
     T_out = (T_in + 2 * (K // 2) - K) // 2 + 1 if stride == 2 else (2 * T_in if upsample else T_in)
     if out is not None:
         y, st = out
@@ -89,7 +98,7 @@ def conv1d(x0, weight, bias=None, *, x1=None, gscale=None, gshift=None, silu=Fal
         f.gamma, f.beta, f.mean_rstd = _p(gn_fold[4]), _p(gn_fold[5]), _p(gn_fold[6])
         d.gn_fold = C.pointer(f)
     pmode = _lib.PACK_MODE[wfmt]
-    wp = pack_conv_weight(weight, pmode)
+    wp = pack_conv_weight(weight, pmode, geometry=(C_out, C0 + C1))
     if skip is not None:
         sx0, sx1, wsk, bsk = skip
         assert residual is None
@@ -138,6 +147,30 @@ def head_conv(x, weight, bias, gscale=None, gshift=None, c_out=None, c_skip=None
     y = torch.empty(B, Cout, T, device=x.device) if out is None else out
     check(lib.tq_head_conv_fwd(_p(x), _p(gscale), _p(gshift), _p(weight.contiguous()), _p(bias), _p(c_out), _p(c_skip),
                                _p(skip_src), _p(y), B, T, Cin, Cout, K, _stream(x.device)), "head")
+    return y
+
+
+def nct_to_btc(x_nct, scale=None, cond_nct=None, Cp=None, out=None):
+    """(B, C0, T) [* scale[b]] ++ (B, C1, T) -> channels-last (B, T, Cp), channels >= C0 + C1 zero (tq_nct_to_btc); ``Cp`` defaults
+    to C0 + C1 rounded up to a multiple of 32.  ``out``: caller-owned (B, T, Cp) tensor to write into."""
+    lib = _lib.load()
+    B, C0, T = x_nct.shape
+    C1 = 0 if cond_nct is None else cond_nct.shape[1]
+    if Cp is None:
+        Cp = (C0 + C1 + 31) // 32 * 32 if out is None else out.shape[2]
+    y = torch.empty(B, T, Cp, device=x_nct.device) if out is None else out
+    check(lib.tq_nct_to_btc(_p(x_nct.contiguous()), _p(scale), _p(None if cond_nct is None else cond_nct.contiguous()), _p(y), B, C0, C1,
+                            T, Cp, _stream(x_nct.device)), "nct_to_btc")
+    return y
+
+
+def btc_to_nct(v_btc, C, c_off=0, a=None, s=None, skip_src=None, out=None):
+    """channels [c_off, c_off + C) of (B, T, Cp) -> (B, C, T): y = v * a[b] + s[b] * skip_src (tq_btc_to_nct; ``a`` and the pair
+    (``s``, ``skip_src``) optional).  ``out``: caller-owned (B, C, T) tensor to write into."""
+    lib = _lib.load()
+    B, T, Cp = v_btc.shape
+    y = torch.empty(B, C, T, device=v_btc.device) if out is None else out
+    check(lib.tq_btc_to_nct(_p(v_btc), _p(a), _p(s), _p(skip_src), _p(y), B, T, Cp, c_off, C, _stream(v_btc.device)), "btc_to_nct")
     return y
 
 
@@ -198,14 +231,17 @@ from ._lib import TQ_BWD_ACCUM, TQ_BWD_DROPOUT, TQ_BWD_GN, TQ_BWD_SILU, TQ_BWD_S
 
 
 def conv1d_bwd_data(dy, weight, *, x0=None, x1=None, gscale=None, gshift=None, silu=False, stats=False, split=None,
-                    accumulate_into=None, dropout_p=0.0, dropout_seed=0, dropout_site=0, wfmt=0, dy_amax=None):
+                    accumulate_into=None, dropout_p=0.0, dropout_seed=0, dropout_site=0, wfmt=0, dy_amax=None, pad_cin=0):
     """dy (B,T,C_out); weight (C_out, C_in, K) torch layout.  Returns (g0, g1|None, gstats|None).
     ``wfmt``: TQ_WFMT_BF16X3 (0) or TQ_WFMT_F16_MX6 (2: dy scaled into the fp16 range by the power of two that ``dy_amax`` selects --
-    an int32[1] device tensor holding the bit pattern of max|dy|; default: computed here with tq_colsum's amax output)."""
+    an int32[1] device tensor holding the bit pattern of max|dy|; default: computed here with tq_colsum's amax output).
+    Padded ends: dy may carry the weight's output channels rounded up to a multiple of 32 (zero padding), and ``pad_cin`` = the weight's
+    input channels rounded up likewise (the gradient of the padding channels comes out zero)."""
     lib = _lib.load()
     B, T, C_dy = dy.shape
-    C_out, C_in, K = weight.shape
-    assert C_dy == C_out
+    C_out, w_ci, K = weight.shape
+    assert C_dy == C_out or 0 < C_dy - C_out < 32
+    C_in = pad_cin or w_ci
     C0 = C_in if split is None else split
     C1 = C_in - C0
     if accumulate_into is not None:
@@ -234,7 +270,7 @@ def conv1d_bwd_data(dy, weight, *, x0=None, x1=None, gscale=None, gshift=None, s
         if dy_amax is None:
             dy_amax = amax_bits(dy)
         d.dy_amax = dy_amax.data_ptr()
-    wp = pack_conv_weight(weight, _lib.PACK_MODE_T[wfmt])
+    wp = pack_conv_weight(weight, _lib.PACK_MODE_T[wfmt], geometry=(C_dy, C_in))
     check(lib.tq_conv1d_bwd_data(C.byref(d), _p(dy), _p(wp), _p(x0), _p(x1), _p(gscale), _p(gshift), _p(g0), _p(g1), _p(st),
                                  _stream(dy.device)), "conv1d_bwd_data")
     return g0, g1, st
