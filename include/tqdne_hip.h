@@ -489,6 +489,22 @@ int tq_nct_to_btc(const float* x_nct, const float* scale, const float* cond_nct,
 int tq_btc_to_nct(const float* v_btc, const float* a, const float* s, const float* skip_src, float* y_nct, int B, int T, int Cp,
                   int c_off, int C, hipStream_t stream);
 
+/* ---- parameter-free resampling (csrc/resample_plain.hip; added under ABI 8) -------------------------------- */
+/* Downsample / Upsample with use_conv=False (blocks.py:29-108; a model built with conv_resample=False): channels-last fp32 tensors,
+ * 4 | C <= 1024, T_in >= 2 (TQ_ERR_SHAPE otherwise; a null x / y / dy / dx: TQ_ERR_ARG -- both before the device is touched).
+ *   tq_avg_pool2_fwd:   y (B, T_out = T_in / 2, C) = (x[b, 2t] + x[b, 2t+1]) * 0.5f in this association (the bits of avg_pool1d for
+ *     finite inputs); the last row of an odd T_in is dropped.
+ *   tq_nearest_up2_fwd: y (B, T_out = 2 T_in, C), y[b, 2t] = y[b, 2t+1] = x[b, t].
+ *   stats (nullable): (B, ceil(T_out / 128), C, 2) = {sum y, sum y^2} per channel and 128-position slot of the OUTPUT -- what a
+ *     TQ_CONV_STATS epilogue leaves and tq_gn_finalize reads with slot = 128.  A workgroup owns whole (b, slot) rows and adds in a fixed
+ *     order (no atomics): the same input gives the same bits.
+ *   tq_avg_pool2_bwd:   dx (B, T_in, C): dx[b, 2t], dx[b, 2t+1] (+)= 0.5f * dy[b, t] with dy (B, T_in / 2, C); with an odd T_in and
+ *     accumulate == 0 the last row of dx is written as zero (left alone when accumulating).
+ * The gradient of tq_nearest_up2_fwd is tq_pair_sum. */
+int tq_avg_pool2_fwd(const float* x, float* y, float* stats, int B, int T_in, int C, hipStream_t stream);
+int tq_nearest_up2_fwd(const float* x, float* y, float* stats, int B, int T_in, int C, hipStream_t stream);
+int tq_avg_pool2_bwd(const float* dy, float* dx, int B, int T_in, int C, int accumulate, hipStream_t stream);
+
 /* ---- optimizer (edm.py:240-251, ema.py:24-28) ------------------------------------------------------------- */
 /* One launch for the whole model: torch.optim.Adam's update (no weight decay, no amsgrad) on every chunk of the table,
  *   g' = g * grad_scale;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;

@@ -216,6 +216,9 @@ _PROTOS = {
     "tq_boundary_max_channels": (I, []),
     "tq_nct_to_btc": (I, [VP] * 4 + [I] * 5 + [VP]),
     "tq_btc_to_nct": (I, [VP] * 5 + [I] * 5 + [VP]),
+    "tq_avg_pool2_fwd": (I, [VP, VP, VP, I, I, I, VP]),
+    "tq_nearest_up2_fwd": (I, [VP, VP, VP, I, I, I, VP]),
+    "tq_avg_pool2_bwd": (I, [VP, VP, I, I, I, I, VP]),
 }
 
 def lib_path() -> str:

@@ -21,8 +21,8 @@ from .unet import AttentionParams, DownsampleParams, ResBlockParams, UpsamplePar
 
 
 def _check(dims, conv_resample):
-    if dims not in (1, 2) or not conv_resample:
-        raise NotImplementedError("tqdne_amd autoencoder: conv-resample, dims=1 (HIP path) or dims=2 (stock-PyTorch family)")
+    if dims not in (1, 2):
+        raise NotImplementedError("tqdne_amd autoencoder: dims=1 (HIP path) or dims=2 (stock-PyTorch family)")
     if dims == 2:
         from . import family2d
         family2d.announce()
@@ -49,7 +49,7 @@ class Encoder(nn.Module):
                 if ds in attention_resolutions:
                     blocks.append(AttentionParams(ch, num_heads, dims))
             if level != len(channel_mult) - 1:
-                blocks.append(DownsampleParams(ch, ch, dims=dims))  # kernel 3 (blocks.py:337 passes none)
+                blocks.append(DownsampleParams(ch, ch, dims=dims, use_conv=conv_resample))  # kernel 3 (blocks.py:337 passes none)
                 ds *= 2
         self.down_blocks = nn.Sequential(*blocks)
         self.output_layer = _conv(dims)(ch, out_channels, k, padding="same")
@@ -91,7 +91,7 @@ class Decoder(nn.Module):
         ds, blocks = 2 ** (len(channel_mult) - 1), []
         for level, mult in reversed(list(enumerate(channel_mult))):
             if level != len(channel_mult) - 1:
-                blocks.append(UpsampleParams(ch, ch, dims=dims))  # kernel 3 (blocks.py:408 passes none)
+                blocks.append(UpsampleParams(ch, ch, dims=dims, use_conv=conv_resample))  # kernel 3 (blocks.py:408 passes none)
                 ds //= 2
             for _ in range(num_res_blocks):
                 blocks.append(ResBlockParams(ch, None, dropout, int(mult * model_channels), k, dims))

@@ -9,7 +9,8 @@ Fusion map (reference op chain -> launches), per block:
   ResBlock (unet.py:131-143):  gn_finalize | conv1[GN+SiLU -> k5 -> +bias +emb, stats] | gn_finalize |
                                (1x1 skip conv) | conv2[GN+SiLU(+dropout) -> k5 -> +bias +skip, stats]
   AttentionBlock (blocks.py:139-145): gn_finalize | qkv conv[GN -> k1] | flash attention | proj conv[k1 + x, stats]
-  Downsample / Upsample (blocks.py:29-108): one conv (stride 2 / nearest-x2 folded into the gather)
+  Downsample / Upsample (blocks.py:29-108): one conv (stride 2 / nearest-x2 folded into the gather); without a conv
+                               (conv_resample=False) one streaming launch that also leaves the output's statistics
   th.cat([h, hs.pop()]) (unet.py:396): never materialised, consumers read two sources.
 """
 
@@ -591,6 +592,21 @@ class UNetEngine:
             self.last_rec.poly = (self.poly_sites[-1][0], self._last_poly_desc)
         return out
 
+    def _resample_plain(self, x: Act, name: str, up: bool) -> Act:
+        """Downsample / Upsample of a conv_resample=False model (blocks.py:56-66,100-108 with use_conv=False): the mean of every pair of
+        positions (an odd last one is dropped) / every position twice, as ONE streaming launch that also leaves the output's partial
+        statistics at the default slot -- the tensor feeds a GroupNorm (for a Downsample also as the second, skip-stack source of a
+        concatenated one) like a conv's output does.  Tape kinds "down_plain" / "up_plain": no parameters, no ConvRec."""
+        if x.C % 4 or x.C > 1024 or x.T < 2:
+            raise NotImplementedError(f"{name}: parameter-free resampling of a ({x.T}, {x.C}) tensor; the HIP kernels take 4 | C <= 1024 and "
+                                      "at least two positions")
+        out = self._act(x.C, 2 * x.T if up else x.T // 2, True)
+        fn, what = (self.lib.tq_nearest_up2_fwd, "nearest_up2:") if up else (self.lib.tq_avg_pool2_fwd, "avg_pool2:")
+        self._emit((fn, (_p(x.buf), _p(out.buf), _p(out.stats), self.B, x.T, x.C), what + name, 0),
+                   nbytes=4 * self.B * x.C * (x.T + out.T))
+        self.tape.append(("up_plain" if up else "down_plain", dict(x=x, out=out)))
+        return out
+
     def _polyphase_op(self, site: ConvSite, d: TqConvDesc, s0: Act, s1: Optional[Act], out: Act, flops: int):
         """Inference form of Upsample (blocks.py:56-66: F.interpolate(nearest, x2), then conv k = 5): both output phases as ONE k = 3
         conv over the un-upsampled rows (TQ_CONV_POLY2) -- even outputs use the taps (w0+w1, w2+w3, w4), odd ones (w0, w1+w2,
@@ -653,6 +669,9 @@ class UNetEngine:
             self._keep.append(d)
             self.emb_desc = d
         self.emb_all = self._empty(B, self.emb_total)
+        # cond_emb_scale (unet.py:216-221,385-388): the single conditioning feature goes through a Fourier projection of its own; its
+        # (B, model_channels) features are what cond_mlp (and the embedding backward) reads
+        self.cond_four = self._empty(B, m.model_channels) if getattr(m, "cond_embed", None) is not None else None
 
         # stem (dynamic args: x, in_scale) -------------------------------------------------------
         stem = m.input_blocks[0][0]
@@ -669,6 +688,10 @@ class UNetEngine:
                     h = self._res_block(h, layer, pfx)
                 elif kind == "attn":
                     h = self._attention(h[0] if isinstance(h, tuple) else h, layer, pfx)
+                elif kind == "down" and not layer.use_conv:
+                    h = self._resample_plain(h, pfx, up=False)
+                elif kind == "up" and not layer.use_conv:
+                    h = self._resample_plain(h, pfx, up=True)
                 elif kind == "down":
                     x_in = h
                     h = self._conv([h], self._site(pfx + ".op", layer.op), stride=2)
@@ -792,7 +815,13 @@ class UNetEngine:
             lse = self._empty(self.B, ab.num_heads, x.T)
         flops = 4 * ab.channels * x.T * x.T * self.B
         fwd = self.lib.tq_attention_fwd_hd if hd else self.lib.tq_attention_fwd   # (same arguments; inference and training share it for hd)
-        op = (fwd, (_p(qkv.buf), _p(att.buf), _p(lse), _p(ws), self.B, x.T, ab.num_heads, D), "attention", flops)
+        # The first-generation and padded-tile kernels (every head size but 32 / 64) deal the key tiles over several workgroups when they are
+        # given the workspace and their grid is far below the chip -- a factor taken from the grid, i.e. from the batch.  Like the small tile
+        # it is a choice of launch-bound plans only, by the same rule: a lane of 8 samples would otherwise split where the one-lane plan of
+        # 16 does not (4 heads of 16 channels at T = 128: 64 against 128 workgroups), and the lane-versus-one-lane bit-identity would be gone
+        launch_bound = self.B <= SMALL_TILE_B or (self.solo and self.B * ((x.T + 127) // 128) <= SMALL_TILE_WGS)
+        ws_fwd = ws if (split is not None or launch_bound) else None
+        op = (fwd, (_p(qkv.buf), _p(att.buf), _p(lse), _p(ws_fwd), self.B, x.T, ab.num_heads, D), "attention", flops)
         if split is not None and not self.ckpt:   # (see enable_block_kv: once a backward plan exists this launch gets a workspace of its own)
             self._attn_train_ops.append((len(self.ops), len(self.tape), ws.numel()))
         infer_op = None
@@ -1054,6 +1083,8 @@ class UNetEngine:
         if cond is not None:
             cond = cond.contiguous().float()
             ncond = cond.shape[1]
+            if cond.shape[0] != B or (self.cond_four is not None and ncond != 1):
+                raise ValueError(f"cond must have shape ({B}, {m.cond_features}), got {tuple(cond.shape)}")
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         self._range_poll(True)
         self.repack(stream)
@@ -1068,8 +1099,13 @@ class UNetEngine:
         ev = (lambda: _recorded_event()) if trace is not None else None
         e0 = ev() if ev else None
         tm, cm = m.time_mlp, (m.cond_mlp if m.cond_features is not None else None)
+        cond_in = cond
+        if self.cond_four is not None:   # [sin(2 pi c W) | cos(2 pi c W)] of cond.view(B), the time embedding's fp32 grouping
+            check(lib.tq_fourier_features(_p(cond), _p(m.cond_embed.W), _p(self.cond_four), B, m.model_channels // 2, stream),
+                  "fourier features of cond")
+            cond_in, ncond = self.cond_four, m.model_channels
         check(lib.tq_embed_fwd(
-            _p(timesteps), _p(cond), _p(m.time_embed.W), _p(tm[0].weight), _p(tm[0].bias), _p(tm[2].weight), _p(tm[2].bias),
+            _p(timesteps), _p(cond_in), _p(m.time_embed.W), _p(tm[0].weight), _p(tm[0].bias), _p(tm[2].weight), _p(tm[2].bias),
             _p(cm[0].weight) if cm else None, _p(cm[0].bias) if cm else None, _p(cm[2].weight) if cm else None,
             _p(cm[2].bias) if cm else None, _p(self.emb), _p(self.silu_emb), _p(self.emb_hidden), B, m.model_channels,
             ncond, stream), "embed")
@@ -1183,6 +1219,10 @@ class SeqEngine(UNetEngine):
                 h = self._res_block(h, layer, pfx)
             elif kind == "attn":
                 h = self._attention(h, layer, pfx)
+            elif kind == "down" and not layer.use_conv:
+                h = self._resample_plain(h, pfx, up=False)
+            elif kind == "up" and not layer.use_conv:
+                h = self._resample_plain(h, pfx, up=True)
             elif kind == "down":
                 x_in = h
                 h = self._conv([h], self._site(pfx + ".op", layer.op), stride=2)

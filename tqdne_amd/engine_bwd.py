@@ -7,6 +7,7 @@ Per block (reverse of the fusion map in engine.py):
   AttentionBlock  wgrad/dgrad(proj) | attention_bwd (dq pass, dk/dv pass) | wgrad(qkv) | dgrad(qkv)[GN sums] |
                   gn_bwd_finalize | gn_bwd_apply (+ residual)
   Downsample      wgrad(stride 2) | zero_stuff + stride-1 dgrad      Upsample   wgrad(upsampled gather) | dgrad + pair_sum
+  (conv_resample=False: Downsample = avg_pool2_bwd, Upsample = pair_sum -- one launch each, no parameters)
   head / stem     dedicated small kernels
 The tiny (B x 256) embedding-MLP backward is four launches of a job-table fp32 GEMM kernel (tq_gemm_f32_jobs, _embedding_jobs).
 Tensors consumed twice (the UNet skip stack) get their gradient written by the first consumer met in the reverse
@@ -112,6 +113,8 @@ class BackwardPlan:
                 mark([p for name, p in t["rb"].named_parameters() if not name.startswith("emb_layers")], pos)
             elif kind == "attn":
                 mark(t["ab"].parameters(), pos)
+            elif kind in ("down_plain", "up_plain"):
+                pass   # (parameter-free resampling: nothing becomes final here)
             else:
                 mark([t["rec"].site.weight, t["rec"].site.bias], pos)
         stem = m.input_blocks[0][0] if hasattr(m, "input_blocks") else m.input_layer
@@ -584,6 +587,22 @@ class BackwardPlan:
         self._wrote(x.grad)
         x.gw = True
 
+    def _bwd_down_plain(self, t):
+        """Downsample without a conv (mean of every pair of positions): both positions get half of the output's gradient"""
+        x, out = t["x"], t["out"]
+        assert out.gw
+        self.ops.append([self.lib.tq_avg_pool2_bwd, [_p(out.grad), _p(self.grad(x)), self.B, x.T, x.C, int(x.gw)], "avg_pool2_bwd"])
+        self._wrote(x.grad)
+        x.gw = True
+
+    def _bwd_up_plain(self, t):
+        """Upsample without a conv (every position twice): the sum of the two copies' gradients"""
+        x, out = t["x"], t["out"]
+        assert out.gw
+        self.ops.append([self.lib.tq_pair_sum, [_p(out.grad), _p(self.grad(x)), self.B, x.T, x.C, int(x.gw)], "pair_sum"])
+        self._wrote(x.grad)
+        x.gw = True
+
     # ------------------------------------------------------------------ run
     def _input_gradient(self, last, stream):
         """d loss / d x (B, C_in, T) of the last forward: the stem conv's data gradient (reference: plain autograd through
@@ -787,7 +806,8 @@ class BackwardPlan:
         if cm is not None:
             self.dc0 = self._empty(B, E)
             c0 = e.emb_hidden[:, 1]
-            self.cond_buf = self._empty(B, m.cond_features)
+            # (cond_emb_scale: cond_mlp read the Fourier features of cond, which the forward left in a static buffer; cond_embed.W is frozen)
+            self.cond_buf = e.cond_four if e.cond_four is not None else self._empty(B, m.cond_features)
 
         def job(A, sam, sak, Bm, sbk, sbn, Cm, ldc, M, N, K, U=None, ldu=0, pre_b=0):
             jb = TqGemmJob()
@@ -817,7 +837,7 @@ class BackwardPlan:
         lv3 = [job(_p(self.dh0), 1, E, _p(self.four), mc, 1, _p(self.gv(tm[0].weight)), mc, E, mc, B),
                job(_p(ones), 0, 1, _p(self.dh0), E, 1, _p(self.gv(tm[0].bias)), E, 1, E, B)]
         if cm is not None:
-            nc = m.cond_features
+            nc = self.cond_buf.shape[1]
             lv2 += [job(_p(self.d_emb), 1, E, _p(c0), hid, 1, _p(self.gv(cm[2].weight)), E, E, E, B, pre_b=1),
                     job(_p(ones), 0, 1, _p(self.d_emb), E, 1, _p(self.gv(cm[2].bias)), E, 1, E, B),
                     job(_p(self.d_emb), E, 1, _p(cm[2].weight), E, 1, _p(self.dc0), E, B, E, E, U=_p(c0), ldu=hid)]
@@ -843,7 +863,7 @@ class BackwardPlan:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         check(lib.tq_fourier_features(_p(last["timesteps"]), _p(m.time_embed.W), _p(self.four), self.B, m.model_channels // 2, stream),
               "fourier features")
-        if m.cond_features is not None:
+        if m.cond_features is not None and e.cond_four is None:
             self.cond_buf.copy_(last["cond"])
         for table, n, total in self._gemm_levels:
             check(lib.tq_gemm_f32_jobs(table.data_ptr(), n, total, stream), "embedding backward GEMMs")

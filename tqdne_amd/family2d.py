@@ -74,16 +74,19 @@ def apply_layer(layer, x: th.Tensor, emb: Optional[th.Tensor]) -> th.Tensor:
         return res_block(layer, x, emb)
     if kind == "attn":
         return attention_block(layer, x)
-    if kind == "down":
-        return layer.op(x)
+    if kind == "down":   # blocks.py:100-108: strided conv, or (conv_resample=False) the mean over 2 x 2 positions
+        return layer.op(x) if layer.use_conv else F.avg_pool2d(x, 2, 2)
     if kind == "up":
-        return layer.conv(F.interpolate(x, scale_factor=2, mode="nearest"))
+        x = F.interpolate(x, scale_factor=2, mode="nearest")
+        return layer.conv(x) if layer.use_conv else x
     return layer(x)   # the stem convolution
 
 
 def unet_forward(m, x: th.Tensor, timesteps: th.Tensor, cond: Optional[th.Tensor]) -> th.Tensor:
     emb = m.time_mlp(fourier_features(m.time_embed.W, timesteps))
     if m.cond_features is not None:
+        if m.cond_embed is not None:   # cond_emb_scale (unet.py:385-388): Fourier features of the single conditioning feature
+            cond = fourier_features(m.cond_embed.W, cond.reshape(cond.shape[0]))
         emb = emb + m.cond_mlp(cond)
     h = x
     saved = []

@@ -398,6 +398,43 @@ def pair_sum(d_up, accumulate_into=None):
     return dx
 
 
+def avg_pool2(x, stats=True, out=None):
+    """Downsample without a conv (blocks.py:100-108, use_conv=False): x (B, T, C) -> (y (B, T // 2, C), statistics | None).
+    ``out`` = (y, statistics | None): caller-owned result buffers."""
+    lib = _lib.load()
+    B, T_in, Cn = x.shape
+    if out is not None:
+        y, st = out
+    else:
+        y = torch.empty(B, T_in // 2, Cn, device=x.device)
+        st = torch.empty(B, nslots(T_in // 2), Cn, 2, device=x.device) if stats else None
+    check(lib.tq_avg_pool2_fwd(_p(x), _p(y), _p(st), B, T_in, Cn, _stream(x.device)), "avg_pool2")
+    return y, st
+
+
+def nearest_up2(x, stats=True, out=None):
+    """Upsample without a conv (blocks.py:56-66, use_conv=False): x (B, T, C) -> (y (B, 2 T, C), statistics | None); ``out`` as above."""
+    lib = _lib.load()
+    B, T_in, Cn = x.shape
+    if out is not None:
+        y, st = out
+    else:
+        y = torch.empty(B, 2 * T_in, Cn, device=x.device)
+        st = torch.empty(B, nslots(2 * T_in), Cn, 2, device=x.device) if stats else None
+    check(lib.tq_nearest_up2_fwd(_p(x), _p(y), _p(st), B, T_in, Cn, _stream(x.device)), "nearest_up2")
+    return y, st
+
+
+def avg_pool2_bwd(dy, T_in, accumulate_into=None):
+    """gradient of avg_pool2 with respect to its (B, T_in, C) input; T_in in (2 T_out, 2 T_out + 1)"""
+    lib = _lib.load()
+    B, T_out, Cn = dy.shape
+    assert T_in // 2 == T_out
+    dx = accumulate_into if accumulate_into is not None else torch.empty(B, T_in, Cn, device=dy.device)
+    check(lib.tq_avg_pool2_bwd(_p(dy), _p(dx), B, T_in, Cn, int(accumulate_into is not None), _stream(dy.device)), "avg_pool2_bwd")
+    return dx
+
+
 def stem_conv_bwd_weight(dy, x_nct, wshape, in_scale=None, workspace=True):
     """``workspace``: two-stage sums through a scratch buffer (default) instead of atomics onto the 30 cache lines of dw"""
     lib = _lib.load()

@@ -88,25 +88,30 @@ class AttentionParams(nn.Module):
 
 
 class DownsampleParams(nn.Module):
-    """blocks.py:69-108 with use_conv=True: conv k (default 3), stride 2, padding k//2."""
+    """blocks.py:69-108.  use_conv=True: conv k (default 3), stride 2, padding k//2.  use_conv=False: the mean of every pair of positions
+    (avg_pool, kernel 2, stride 2) -- no ``op``, no parameters, no state_dict keys."""
 
     kind = "down"
 
-    def __init__(self, channels, out_channels=None, kernel_size=3, dims=1):
+    def __init__(self, channels, out_channels=None, kernel_size=3, dims=1, use_conv=True):
         super().__init__()
-        self.channels, self.out_channels = channels, out_channels or channels
-        self.op = _conv(dims)(channels, self.out_channels, kernel_size, stride=2, padding=kernel_size // 2)
+        self.channels, self.out_channels, self.use_conv = channels, out_channels or channels, use_conv
+        if use_conv:
+            self.op = _conv(dims)(channels, self.out_channels, kernel_size, stride=2, padding=kernel_size // 2)
+        else:
+            assert self.channels == self.out_channels   # (blocks.py:95)
 
 
 class UpsampleParams(nn.Module):
-    """blocks.py:29-66 with use_conv=True: nearest x2 then "same" conv."""
+    """blocks.py:29-66.  use_conv=True: nearest x2 then "same" conv.  use_conv=False: nearest x2 alone -- no ``conv``, no parameters."""
 
     kind = "up"
 
-    def __init__(self, channels, out_channels=None, kernel_size=3, dims=1):
+    def __init__(self, channels, out_channels=None, kernel_size=3, dims=1, use_conv=True):
         super().__init__()
-        self.channels, self.out_channels = channels, out_channels or channels
-        self.conv = _conv(dims)(channels, self.out_channels, kernel_size, padding="same")
+        self.channels, self.out_channels, self.use_conv = channels, out_channels or channels, use_conv
+        if use_conv:
+            self.conv = _conv(dims)(channels, self.out_channels, kernel_size, padding="same")
 
 
 class BlockSeq(nn.Sequential):
@@ -137,8 +142,14 @@ class UNetModel(nn.Module):
         super().__init__()
         if dims not in (1, 2):
             raise NotImplementedError("tqdne_amd.UNetModel: dims=1 (the HIP hot path) or dims=2 (stock-PyTorch family, family2d.py)")
-        if use_scale_shift_norm or cond_emb_scale is not None or not conv_resample or use_causal_mask:
+        if use_scale_shift_norm or use_causal_mask:
             raise NotImplementedError("option unused by every reference config of the supported families and not implemented")
+        if cond_emb_scale is not None and cond_features != 1:
+            # blocks.py:22-26 multiplies x[:, None] by W[None, :]: a (B, F) conditioning vector broadcasts only for F = 1 (F = model_channels / 2
+            # broadcasts too, but then the flattened features no longer match cond_mlp), so the reference's own forward cannot run it either
+            raise NotImplementedError(
+                f"cond_emb_scale with cond_features={cond_features}: the Fourier projection of the conditioning vector takes exactly one "
+                "conditioning feature (the reference's own forward fails for every other count as well)")
         self.dims = dims
         if dims == 2:
             from . import family2d
@@ -150,14 +161,18 @@ class UNetModel(nn.Module):
         self.num_res_blocks, self.attention_resolutions = num_res_blocks, tuple(attention_resolutions)
         self.dropout, self.channel_mult, self.conv_kernel_size = dropout, tuple(channel_mult), conv_kernel_size
         self.num_heads, self.use_checkpoint = num_heads, use_checkpoint
+        self.conv_resample, self.cond_emb_scale = bool(conv_resample), cond_emb_scale
 
         embed_dim = model_channels * 4
         self.time_embed = FourierParams(model_channels)
         self.time_mlp = nn.Sequential(nn.Linear(model_channels, embed_dim), nn.SiLU(), nn.Linear(embed_dim, embed_dim))
         self.cond_features = cond_features
         if cond_features is not None:
-            self.cond_embed = None
-            self.cond_mlp = nn.Sequential(nn.Linear(cond_features, embed_dim), nn.SiLU(), nn.Linear(embed_dim, embed_dim))
+            # unet.py:216-221: with cond_emb_scale the conditioning goes through a Fourier projection of its own (drawn between time_mlp
+            # and cond_mlp) and cond_mlp reads cond_features * model_channels features
+            self.cond_embed = FourierParams(model_channels, cond_emb_scale) if cond_emb_scale is not None else None
+            cond_in = cond_features * model_channels if cond_emb_scale is not None else cond_features
+            self.cond_mlp = nn.Sequential(nn.Linear(cond_in, embed_dim), nn.SiLU(), nn.Linear(embed_dim, embed_dim))
 
         k = conv_kernel_size
         ch = input_ch = int(channel_mult[0] * model_channels)
@@ -173,7 +188,7 @@ class UNetModel(nn.Module):
                 self.input_blocks.append(BlockSeq(*layers))
                 skip_chans.append(ch)
             if level != len(channel_mult) - 1:
-                self.input_blocks.append(BlockSeq(DownsampleParams(ch, ch, dims=dims)))  # kernel 3: unet.py:273 passes none
+                self.input_blocks.append(BlockSeq(DownsampleParams(ch, ch, dims=dims, use_conv=conv_resample)))  # kernel 3: unet.py:273 passes none
                 skip_chans.append(ch)
                 ds *= 2
 
@@ -191,7 +206,7 @@ class UNetModel(nn.Module):
                 if ds in self.attention_resolutions:
                     layers.append(AttentionParams(ch, num_heads, dims))
                 if level and i == num_res_blocks:
-                    layers.append(UpsampleParams(ch, ch, k, dims))
+                    layers.append(UpsampleParams(ch, ch, k, dims, use_conv=conv_resample))
                     ds //= 2
                 self.output_blocks.append(BlockSeq(*layers))
 
