@@ -640,6 +640,16 @@ def test_more_than_64_signal_channels_are_refused_when_the_plan_is_built(cin, co
         m._engine(2, 64, dev())
 
 
+def test_a_decoder_output_of_24_channels_is_refused_when_the_plan_is_built():
+    """an Encoder / Decoder output layer is not padded like the UNet's wide head: beyond the head kernel's 16 channels only multiples of 32"""
+    from tqdne_amd import Decoder
+    torch.manual_seed(0)
+    _, dec_cfg = ae_cfgs(signal=24, latent=16)
+    dec = Decoder(**dec_cfg).to(dev()).eval()
+    with pytest.raises(NotImplementedError, match=r"output_layer: 24 channels"):
+        dec(torch.randn(2, 16, 64, device=dev()))
+
+
 def test_the_dedicated_kernels_still_refuse_17_signal_channels():
     from tqdne_amd import ops
     from tqdne_amd._lib import TqError

@@ -173,10 +173,14 @@ def pack_batch(lib, dev, jobs, stream, capturing=False):
     check(lib.tq_pack_jobs(table.data_ptr(), n, total, stream), "pack jobs")
 
 
+_HIP_RUNTIME = None
+
+
 def _lib_copy_floats(dst, src, n, stream):
-    import ctypes
-    rt = ctypes.CDLL("libamdhip64.so")
-    rc = rt.hipMemcpyAsync(ctypes.c_void_p(dst), ctypes.c_void_p(src), ctypes.c_size_t(4 * n), 3, ctypes.c_void_p(stream))
+    global _HIP_RUNTIME
+    if _HIP_RUNTIME is None:
+        _HIP_RUNTIME = C.CDLL("libamdhip64.so")
+    rc = _HIP_RUNTIME.hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(4 * n), 3, C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"hipMemcpyAsync failed: {rc}")
 
@@ -264,6 +268,15 @@ def _check_head_limits(C_in: int, C_out: int, k: int, name: str = "out.2"):
         raise NotImplementedError(
             f"output conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP head kernels take C_in = 16, 32, 48, ... 128 or a multiple of "
             "32 up to 1024, C_out <= 16 and k in (1, 3, 5)")
+
+
+def _check_unpadded_head(C_out: int, name: str):
+    """An Encoder / Decoder output layer beyond the head kernel's 16 channels is an ordinary conv site followed by a layout flip; unlike
+    the UNet's wide head it is not padded, so its width must be one the conv kernels write: a multiple of 32."""
+    if C_out > NARROW_SIGNAL_CHANNELS and C_out % 32:
+        raise NotImplementedError(
+            f"output conv {name}: {C_out} channels: the HIP path takes up to 16 output channels (head kernel) or a multiple of 32 (the "
+            "generic conv, not padded at this end) for an Encoder / Decoder")
 
 
 def _check_stem_limits(C_in: int, C_out: int, k: int, name: str = "input_blocks.0.0"):
@@ -379,7 +392,24 @@ class UNetEngine:
         self._bwd = None
         self.dgrad_sites = []
         self._wt_version = None
+        self._last = None                   # arguments of the most recent forward (what its backward needs)
+        self._fwd_count = 0
+        self._site_counter = 0              # dropout site numbers of the ResBlocks, in execution order
+        self._pending_gn = None             # a GroupNorm whose finalisation the next conv places (see _gn, defer)
+        self._fold_default_ops = []         # (index into ops, tq_gn_finalize, descriptor) of default-tile convs that fold their GroupNorm
+        self.gn_folded = 0
+        self._last_poly_desc = None
+        self._attn_ws = self._attn_ws_hd = None
+        # the embedding (plans of a UNet; an Encoder / Decoder has none)
+        self.res_blocks, self.emb_offsets, self.emb_total = [], {}, 0
+        self.emb_desc, self.emb_entry, self.emb_pack_mode, self.cond_four = None, None, 0, None
+        # the two ends: set by _stem / _wide_head / the plan's _build
+        self.wide_stem = self.wide_head = False
+        self.x_btc = self.stem_out = self.stem_rec = None
+        self.final = self.head_gn = self.head_btc = self.head_rec = self.out_nct = None
+        self.out_mode = "head"              # "head": the dedicated kernel; "wide": padded conv + tq_btc_to_nct; "conv": conv + layout flip
         self._build()
+        assert self._pending_gn is None, "a deferred GroupNorm finalisation was never placed"
         if getattr(model, "_conv_scheme", "auto") == "bf16x3":
             self._set_scheme_bf16x3()
 
@@ -435,6 +465,12 @@ class UNetEngine:
         self.ops_infer.append(op if infer_op is None else infer_op)
         self.op_bytes.append(nbytes)
 
+    def _launch_bound(self, T_out: int) -> bool:
+        """Is a launch over ``T_out`` positions one of a launch-bound plan?  The one rule behind the small tile, the channel-tiled qkv
+        projection and the attention key split (see SMALL_TILE_B / SMALL_TILE_WGS, read when called: tests set them at run time); the
+        lane-versus-one-lane bit-identity rests on the three sites sharing it."""
+        return self.B <= SMALL_TILE_B or (self.solo and self.B * ((T_out + 127) // 128) <= SMALL_TILE_WGS)
+
     def _gn(self, srcs: Sequence[Act], norm: torch.nn.GroupNorm, defer: bool = False):
         """Folded scale / shift (B, C) of a GroupNorm over the (concatenated) sources: a tq_gn_finalize launch, or (``defer``) the
         consuming conv's own prologue where that conv folds (see ``_conv``)."""
@@ -478,7 +514,7 @@ class UNetEngine:
         _check_width_limits(site.name, site.C_in, site.C_out)
         wfmt = _lib.forward_wfmt(site.C_out, srcs_c, stride, upsample, k5_act=k5_act, gn=gn is not None) if launch else 0
         # the small tile where it is built (see SMALL_TILE_B): the ResBlock convs of a small-batch plan
-        small = (launch and (self.B <= SMALL_TILE_B or (self.solo and self.B * ((T_out + 127) // 128) <= SMALL_TILE_WGS)) and k5_act
+        small = (launch and self._launch_bound(T_out) and k5_act
                  and wfmt in (_lib.TQ_WFMT_BF16X3, _lib.TQ_WFMT_F16_MX6))
         if small and wfmt == _lib.TQ_WFMT_F16_MX6 and site.C_out % 128:
             wfmt = _lib.TQ_WFMT_BF16X3   # (the small tile's fp16 + MX-fp6 form is the 128-channel one)
@@ -488,7 +524,7 @@ class UNetEngine:
             out = self._act(site.C_out, T_out, stats, slot=32 if small else STAT_SLOT) if launch else None
         d = TqConvDesc()
         d.t_tile = 32 if small else 0
-        pend = getattr(self, "_pending_gn", None)
+        pend = self._pending_gn
         if pend is not None and gn is not None and pend["key"] == gn[0].data_ptr():
             self._pending_gn = None
             # (the fold only where the library's tile takes it at this width -- its scratch must fit the tile's staging buffers; a
@@ -503,7 +539,6 @@ class UNetEngine:
                 # the tq_gn_finalize launch stays in the plan as a no-op: the range-guard fallback moves this conv to the three-product
                 # scheme, whose default tiles do not fold -- it then gets its launch back (_set_scheme_bf16x3)
                 fn, fargs, fname, ffl = pend["fin"][0]
-                self._fold_default_ops = getattr(self, "_fold_default_ops", [])
                 self._fold_default_ops.append((len(self.ops), fn, d))
                 self._emit((_noop_launch, fargs, fname + " (folded into its consumer)", ffl), nbytes=0)
             if launch and ((small and fold_fits) or fold_default) and not self.ckpt:
@@ -514,7 +549,7 @@ class UNetEngine:
                 f.gamma, f.beta, f.mean_rstd = _p(pend["norm"].weight), _p(pend["norm"].bias), _p(pend["mean_rstd"])
                 self._keep.append(f)
                 d.gn_fold = C.pointer(f)
-                self.gn_folded = getattr(self, "gn_folded", 0) + 1
+                self.gn_folded += 1
             else:
                 self._emit(pend["fin"][0], nbytes=pend["fin"][1])
         d.B, d.T_in, d.T_out = self.B, T_in, T_out
@@ -533,7 +568,7 @@ class UNetEngine:
             assert res.C == site.C_out and res.T == T_out
         if stats:
             flags |= TQ_CONV_STATS
-        if site.K == 1 and (self.B <= SMALL_TILE_B or (self.solo and self.B * ((T_out + 127) // 128) <= SMALL_TILE_WGS)):
+        if site.K == 1 and self._launch_bound(T_out):
             # launch-bound plans (the rule of the small tile): the qkv projection in its channel-tiled form -- the input-stationary one
             # has ONE workgroup per 128 positions (a 16-sample plan at T = 512: 64 on 256 compute units; 37 -> 21 us)
             flags |= _lib.TQ_CONV_CH_TILES
@@ -654,10 +689,8 @@ class UNetEngine:
         self.emb_hidden = self._empty(B, 2, self.E)
         self.emb_w = self.store.entry("emb_w", (self.emb_total, self.E), torch.float32)["buf"]
         self.emb_b = self.store.entry("emb_b", (self.emb_total,), torch.float32)["buf"]
-        self.emb_entry = None
         # all 22 per-block Linear(SiLU(emb)) projections (unet.py:91-97) as ONE pointwise "conv" on the MFMA path: the B samples
         # are the positions of a single (1, B, E) channels-last sequence, the concatenated weight a (emb_total, E, 1) kernel
-        self.emb_desc = None
         if self.emb_total > 0 and self.E % 32 == 0 and self.emb_total % 32 == 0:
             d = TqConvDesc()
             d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = 1, B, B, self.E, 0, self.emb_total
@@ -678,50 +711,50 @@ class UNetEngine:
         self._stem(stem, m.in_channels, T, "input_blocks.0.0")
         hs = [self.stem_out]
         h = self.stem_out
-        self._site_counter = 0
-
-        def run_layers(layers, h, name):
-            for li, layer in enumerate(layers):
-                kind = getattr(layer, "kind", None)
-                pfx = f"{name}.{li}"
-                if kind == "res":
-                    h = self._res_block(h, layer, pfx)
-                elif kind == "attn":
-                    h = self._attention(h[0] if isinstance(h, tuple) else h, layer, pfx)
-                elif kind == "down" and not layer.use_conv:
-                    h = self._resample_plain(h, pfx, up=False)
-                elif kind == "up" and not layer.use_conv:
-                    h = self._resample_plain(h, pfx, up=True)
-                elif kind == "down":
-                    x_in = h
-                    h = self._conv([h], self._site(pfx + ".op", layer.op), stride=2)
-                    self.tape.append(("down", dict(x=x_in, out=h, rec=self.last_rec)))
-                elif kind == "up":
-                    x_in = h
-                    h = self._conv([h], self._site(pfx + ".conv", layer.conv), upsample=True)
-                    self.tape.append(("up", dict(x=x_in, out=h, rec=self.last_rec)))
-                else:
-                    raise RuntimeError(f"unexpected layer {type(layer)} in {name}")
-            return h
-
         for i, blk in enumerate(m.input_blocks):
             if i == 0:
                 continue
-            h = run_layers(blk, h, f"input_blocks.{i}")
+            h = self._layers(blk, h, f"input_blocks.{i}")
             hs.append(h)
-        h = run_layers(m.middle_block, h, "middle_block")
+        h = self._layers(m.middle_block, h, "middle_block")
         for i, blk in enumerate(m.output_blocks):
             skip = hs.pop()
-            h = run_layers(blk, (h, skip), f"output_blocks.{i}")
+            h = self._layers(blk, (h, skip), f"output_blocks.{i}")
         self.final = h
         self.wide_head = m.out[2].out_channels > NARROW_SIGNAL_CHANNELS
         if not self.wide_head:
             _check_head_limits(h.C, m.out[2].out_channels, m.out[2].kernel_size[0])
         self.head_gn = self._gn([h], m.out[0])
         if self.wide_head:
+            self.out_mode = "wide"
             self._wide_head(h, m.out[2], "out.2", self.head_gn)
         self.out_nct = self._empty(B, m.out_channels, T)
-        assert getattr(self, "_pending_gn", None) is None, "a deferred GroupNorm finalisation was never placed"
+
+    def _layers(self, layers, h, name: str):
+        """The launches of one sequence of layers (a block of the UNet, the whole body of an Encoder / Decoder).  ``h``: the input, or
+        (input, skip-stack entry) for a block whose first ResBlock reads the concatenation."""
+        for li, layer in enumerate(layers):
+            kind = getattr(layer, "kind", None)
+            pfx = f"{name}.{li}"
+            if kind == "res":
+                h = self._res_block(h, layer, pfx)
+            elif kind == "attn":
+                h = self._attention(h[0] if isinstance(h, tuple) else h, layer, pfx)
+            elif kind == "down" and not layer.use_conv:
+                h = self._resample_plain(h, pfx, up=False)
+            elif kind == "up" and not layer.use_conv:
+                h = self._resample_plain(h, pfx, up=True)
+            elif kind == "down":
+                x_in = h
+                h = self._conv([h], self._site(pfx + ".op", layer.op), stride=2)
+                self.tape.append(("down", dict(x=x_in, out=h, rec=self.last_rec)))
+            elif kind == "up":
+                x_in = h
+                h = self._conv([h], self._site(pfx + ".conv", layer.conv), upsample=True)
+                self.tape.append(("up", dict(x=x_in, out=h, rec=self.last_rec)))
+            else:
+                raise RuntimeError(f"unexpected layer {type(layer)} in {name}")
+        return h
 
     def _stem(self, stem, cin: int, T: int, name: str):
         """The first conv.  Up to 16 signal channels: the dedicated kernel (tq_stem_conv_fwd, launched by ``forward`` with the dynamic
@@ -747,15 +780,74 @@ class UNetEngine:
         self.head_btc = self._conv([h], site, gn=gn, silu=gn is not None, stats=False)
         self.head_rec = self.last_rec
 
-    def _run_stem(self, x, in_scale, stem, cin, stream, what, cond_x=None):
+    def _run_stem(self, x, in_scale, stem, cin, stream, trace, what, name, cond_x=None):
+        """The launch with the dynamic arguments at the input end (``what``: its name in an error, ``name``: in a trace)."""
+        B, T, co, K = self.B, self.T, stem.out_channels, stem.kernel_size[0]
+        e0 = _recorded_event() if trace is not None else None
         if self.wide_stem:
             c1 = 0 if cond_x is None else cond_x.shape[1]
-            check(self.lib.tq_nct_to_btc(_p(x), _p(in_scale), _p(cond_x), _p(self.x_btc.buf), self.B, cin - c1, c1, self.T, self.x_btc.C,
+            check(self.lib.tq_nct_to_btc(_p(x), _p(in_scale), _p(cond_x), _p(self.x_btc.buf), B, cin - c1, c1, T, self.x_btc.C,
                                          stream), what + " (nct_to_btc)")
+            entry = ("nct_to_btc:" + name, 0, 4 * B * T * (cin + self.x_btc.C))
         else:
             check(self.lib.tq_stem_conv_fwd(_p(x), _p(in_scale), _p(stem.weight), _p(stem.bias), _p(self.stem_out.buf),
-                                            _p(self.stem_out.stats), self.B, cin, self.T, stem.out_channels, stem.kernel_size[0],
-                                            stream), what)
+                                            _p(self.stem_out.stats), B, cin, T, co, K, stream), what)
+            entry = (name, 2 * B * T * cin * co * K, 4 * B * T * (cin + co))
+        if trace is not None:
+            trace.append(entry + (e0, _recorded_event()))
+
+    def _run_head(self, head, epilogue, stream, trace, what, name):
+        """The launch with the dynamic arguments at the output end, into ``out_nct``.  ``epilogue``: (c_out, c_skip, skip_src) of the
+        UNet (each may be None), None for an Encoder / Decoder, whose output layer has neither a GroupNorm nor an epilogue."""
+        B, T, fin, co, K = self.B, self.final.T, self.final, head.out_channels, head.kernel_size[0]
+        c_out, c_skip, skip_src = epilogue or (None, None, None)
+        io = co * (1 if epilogue is None else 2)   # (bytes: the output, and the skip source the UNet's epilogue may read)
+        e0 = _recorded_event() if trace is not None else None
+        if self.out_mode == "head":
+            gn = self.head_gn or (None, None)
+            check(self.lib.tq_head_conv_fwd(_p(fin.buf), _p(gn[0]), _p(gn[1]), _p(head.weight), _p(head.bias), _p(c_out), _p(c_skip),
+                                            _p(skip_src), _p(self.out_nct), B, T, fin.C, co, K, stream), what)
+            entry = (name, 2 * B * T * fin.C * co * K, 4 * B * T * (fin.C + io))
+        elif self.out_mode == "wide":   # (the conv itself was the plan's last launch)
+            check(self.lib.tq_btc_to_nct(_p(self.head_btc.buf), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
+                                         self.head_btc.C, 0, co, stream), "head epilogue (btc_to_nct)")
+            entry = ("btc_to_nct:" + name, 0, 4 * B * T * (self.head_btc.C + io))
+        else:
+            self.out_nct.copy_(self.head_btc.buf.permute(0, 2, 1))  # (B,T,C) -> (B,C,T): 1/60 of the encoder's traffic
+            entry = ("output layout flip", 0, 4 * B * T * (fin.C + io))
+        if trace is not None:
+            trace.append(entry + (e0, _recorded_event()))
+
+    def _arm_dropout(self, p: float, seed: int, descs=None, flag: int = TQ_CONV_DROPOUT):
+        """Probability and seed of the next launches into the forward descriptors with a dropout site -- or into ``descs``, the
+        backward plan's (their flag: TQ_BWD_DROPOUT)."""
+        for d in self.dropout_descs if descs is None else descs:
+            if p > 0.0:
+                d.flags |= flag
+                d.dropout_p, d.dropout_seed = p, seed
+            else:
+                d.flags &= ~flag
+
+    def _run_ops(self, ops, stream, trace):
+        """The plan's launches, in order.  ``trace``: a list that gets HIP events around every launch (measurement only); else the
+        probe, where one is installed, gets them around its one launch."""
+        probe = self._probe
+        if trace is None and (probe is None or torch.cuda.is_current_stream_capturing()):
+            for fn, args, what, _ in ops:   # (plans of <= 4 samples are ~100 dependent launches and bounded by this loop: nothing else in it)
+                rc = fn(*args, stream)
+                if rc:
+                    check(rc, what)
+            return
+        for i, (fn, args, what, fl) in enumerate(ops):
+            timed = trace is not None or i == probe.idx
+            a = _recorded_event() if timed else None
+            rc = fn(*args, stream)
+            if trace is not None:
+                trace.append((what, fl, self.op_bytes[i], a, _recorded_event()))
+            elif timed:
+                probe.events.append((a, _recorded_event()))
+            if rc:
+                check(rc, what)
 
     def _res_block(self, x, rb, name: str) -> Act:
         srcs = list(x) if isinstance(x, tuple) else [x]
@@ -819,8 +911,7 @@ class UNetEngine:
         # given the workspace and their grid is far below the chip -- a factor taken from the grid, i.e. from the batch.  Like the small tile
         # it is a choice of launch-bound plans only, by the same rule: a lane of 8 samples would otherwise split where the one-lane plan of
         # 16 does not (4 heads of 16 channels at T = 128: 64 against 128 workgroups), and the lane-versus-one-lane bit-identity would be gone
-        launch_bound = self.B <= SMALL_TILE_B or (self.solo and self.B * ((x.T + 127) // 128) <= SMALL_TILE_WGS)
-        ws_fwd = ws if (split is not None or launch_bound) else None
+        ws_fwd = ws if (split is not None or self._launch_bound(x.T)) else None
         op = (fwd, (_p(qkv.buf), _p(att.buf), _p(lse), _p(ws_fwd), self.B, x.T, ab.num_heads, D), "attention", flops)
         if split is not None and not self.ckpt:   # (see enable_block_kv: once a backward plan exists this launch gets a workspace of its own)
             self._attn_train_ops.append((len(self.ops), len(self.tape), ws.numel()))
@@ -846,7 +937,7 @@ class UNetEngine:
         stream); a block that needs more (a Decoder with attention at several resolutions: T grows along up_blocks) gets a
         buffer of its own -- launches already emitted keep the pointer they were bound to.  ``slot``: the padded-tile kernels keep
         their key-split rows in a buffer of their own, away from the planes whose padding rows must stay zero"""
-        ws = getattr(self, slot, None)
+        ws = getattr(self, slot)
         if ws is None or ws.numel() != nbytes:
             ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)  # padding rows (t >= T) stay zero
             self._keep.append(ws)
@@ -868,13 +959,13 @@ class UNetEngine:
             d.wfmt = _lib.TQ_WFMT_BF16X3
             for st in sites:
                 st.pack_mode = 0
-        for i, fn, d in getattr(self, "_fold_default_ops", ()):   # default-tile convs that folded their own GroupNorm get the launch back
+        for i, fn, d in self._fold_default_ops:   # default-tile convs that folded their own GroupNorm get the launch back
             for ops in (self.ops, self.ops_infer):
                 _f, a_, w_, fl_ = ops[i]
                 ops[i] = (fn, a_, "gn_finalize", fl_)
             d.gn_fold = None
         self._fold_default_ops = []
-        if getattr(self, "emb_desc", None) is not None:
+        if self.emb_desc is not None:
             self.emb_desc.wfmt = _lib.TQ_WFMT_BF16X3
             self.emb_pack_mode = 0
         # the inference attention pair leaves the fp16 V planes with the convs (its v_format is the last integer of both calls)
@@ -963,7 +1054,7 @@ class UNetEngine:
         emb = None
         if self.emb_total > 0:
             ver = tuple((id(rb.emb_layers[1].weight), rb.emb_layers[1].weight._version, rb.emb_layers[1].bias._version)
-                        for rb in self.res_blocks if hasattr(rb, "emb_layers")) + (getattr(self, "emb_pack_mode", 0),)
+                        for rb in self.res_blocks if hasattr(rb, "emb_layers")) + (self.emb_pack_mode,)
             e = self.store.entries["emb_w"]
             if e["ver"] != ver:
                 emb = ver
@@ -1028,7 +1119,7 @@ class UNetEngine:
                           "pack " + ps.name)
                     ps.entry["ver"] = ver
                 if emb is not None:
-                    if getattr(self, "emb_desc", None) is not None:   # (reads emb_w: stream-ordered behind the gather above)
+                    if self.emb_desc is not None:   # (reads emb_w: stream-ordered behind the gather above)
                         check(lib.tq_pack_conv_weight(self.emb_w.data_ptr(), self.emb_total, self.E, 1, self.emb_pack_mode,
                                                       self.emb_packed.data_ptr(), stream), "pack emb projections")
                     store.entries["emb_w"]["ver"] = emb
@@ -1089,15 +1180,9 @@ class UNetEngine:
         self._range_poll(True)
         self.repack(stream)
         p = float(m.dropout) if train else 0.0
-        for d in self.dropout_descs:
-            if p > 0.0:
-                d.flags |= TQ_CONV_DROPOUT
-                d.dropout_p, d.dropout_seed = p, dropout_seed
-            else:
-                d.flags &= ~TQ_CONV_DROPOUT
+        self._arm_dropout(p, dropout_seed)
         trace = None if torch.cuda.is_current_stream_capturing() else self._trace
-        ev = (lambda: _recorded_event()) if trace is not None else None
-        e0 = ev() if ev else None
+        e0 = _recorded_event() if trace is not None else None
         tm, cm = m.time_mlp, (m.cond_mlp if m.cond_features is not None else None)
         cond_in = cond
         if self.cond_four is not None:   # [sin(2 pi c W) | cos(2 pi c W)] of cond.view(B), the time embedding's fp32 grouping
@@ -1115,63 +1200,15 @@ class UNetEngine:
         else:
             check(lib.tq_linear_fwd(_p(self.silu_emb), _p(self.emb_w), _p(self.emb_b), _p(self.emb_all), B, self.E,
                                     self.emb_total, stream), "emb projections")
-        if ev:
-            e1 = ev()
-            trace.append(("embed", 2 * B * self.E * (self.emb_total + 2 * self.E), 4 * (self.emb_total * self.E + B * self.emb_total), e0, e1))
-            e0 = e1
-        stem = m.input_blocks[0][0]
-        self._run_stem(x, in_scale, stem, m.in_channels, stream, "stem conv", cond_x)
-        if ev:
-            e1 = ev()
-            if self.wide_stem:
-                trace.append(("nct_to_btc:stem", 0, 4 * B * T * (m.in_channels + self.x_btc.C), e0, e1))
-            else:
-                trace.append(("stem", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
-                              4 * B * T * (m.in_channels + stem.out_channels), e0, e1))
-        probe = self._probe
-        ops = self.ops_infer if (infer and not train) else self.ops
         if trace is not None:
-            for i, (fn, args, what, fl) in enumerate(ops):
-                a = ev()
-                rc = fn(*args, stream)
-                b = ev()
-                trace.append((what, fl, self.op_bytes[i], a, b))
-                if rc:
-                    check(rc, what)
-        elif probe is None or torch.cuda.is_current_stream_capturing():
-            for fn, args, what, _ in ops:
-                rc = fn(*args, stream)
-                if rc:
-                    check(rc, what)
-        else:
-            for i, (fn, args, what, _) in enumerate(ops):
-                if i == probe.idx:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    rc = fn(*args, stream)
-                    e1.record()
-                    probe.events.append((e0, e1))
-                else:
-                    rc = fn(*args, stream)
-                if rc:
-                    check(rc, what)
-        self._fwd_count = getattr(self, "_fwd_count", 0) + 1
+            trace.append(("embed", 2 * B * self.E * (self.emb_total + 2 * self.E), 4 * (self.emb_total * self.E + B * self.emb_total), e0,
+                          _recorded_event()))
+        self._run_stem(x, in_scale, m.input_blocks[0][0], m.in_channels, stream, trace, "stem conv", "stem", cond_x)
+        self._run_ops(self.ops_infer if (infer and not train) else self.ops, stream, trace)
+        self._fwd_count += 1
         self._last = dict(x=x, in_scale=in_scale, c_out=c_out, timesteps=timesteps, cond=cond, train=train, c0=m.in_channels - c1,
                           dropout_p=p, dropout_seed=dropout_seed, infer=infer and not train, block_kv=self._block_kv)
-        head = m.out[2]
-        e0 = ev() if ev else None
-        if self.wide_head:   # (the conv itself was the plan's last launch)
-            check(lib.tq_btc_to_nct(_p(self.head_btc.buf), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
-                                    self.head_btc.C, 0, m.out_channels, stream), "head epilogue (btc_to_nct)")
-            if ev:
-                trace.append(("btc_to_nct:head", 0, 4 * B * T * (self.head_btc.C + 2 * m.out_channels), e0, ev()))
-        else:
-            check(lib.tq_head_conv_fwd(_p(self.final.buf), _p(self.head_gn[0]), _p(self.head_gn[1]), _p(head.weight),
-                                       _p(head.bias), _p(c_out), _p(c_skip), _p(skip_src), _p(self.out_nct), B, T,
-                                       self.final.C, m.out_channels, head.kernel_size[0], stream), "head conv")
-            if ev:
-                trace.append(("head", 2 * B * T * self.final.C * m.out_channels * head.kernel_size[0],
-                              4 * B * T * (self.final.C + 2 * m.out_channels), e0, ev()))
+        self._run_head(m.out[2], (c_out, c_skip, skip_src), stream, trace, "head conv", "head")
         if train:
             self._range_poll(False)
         self._mark_use(stream)
@@ -1206,88 +1243,34 @@ class SeqEngine(UNetEngine):
 
     def _build(self):
         m, B, T = self.m, self.B, self.T
-        self.res_blocks, self.emb_offsets, self.emb_total = [], {}, 0
-        self._site_counter = 0
         stem = m.input_layer
         self._stem(stem, stem.in_channels, T, "input_layer")
-        h = self.stem_out
-        blocks = getattr(m, m.blocks_attr)
-        for li, layer in enumerate(blocks):
-            kind = getattr(layer, "kind", None)
-            pfx = f"{m.blocks_attr}.{li}"
-            if kind == "res":
-                h = self._res_block(h, layer, pfx)
-            elif kind == "attn":
-                h = self._attention(h, layer, pfx)
-            elif kind == "down" and not layer.use_conv:
-                h = self._resample_plain(h, pfx, up=False)
-            elif kind == "up" and not layer.use_conv:
-                h = self._resample_plain(h, pfx, up=True)
-            elif kind == "down":
-                x_in = h
-                h = self._conv([h], self._site(pfx + ".op", layer.op), stride=2)
-                self.tape.append(("down", dict(x=x_in, out=h, rec=self.last_rec)))
-            elif kind == "up":
-                x_in = h
-                h = self._conv([h], self._site(pfx + ".conv", layer.conv), upsample=True)
-                self.tape.append(("up", dict(x=x_in, out=h, rec=self.last_rec)))
-            else:
-                raise RuntimeError(f"unexpected layer {type(layer)}")
-        self.final = h
+        h = self.final = self._layers(getattr(m, m.blocks_attr), self.stem_out, m.blocks_attr)
         out = m.output_layer
+        _check_unpadded_head(out.out_channels, "output_layer")
         self.out_nct = self._empty(B, out.out_channels, h.T)
         if out.out_channels <= 16:
             _check_head_limits(h.C, out.out_channels, out.kernel_size[0], "output_layer")
-            self.out_mode = "head"
         else:  # wide output (encoder: 2 x latent channels): fused conv to channels-last, then a layout flip
             self.out_mode = "conv"
-            self.out_btc = self._conv([h], self._site("output_layer", out), stats=False)
-            self.out_rec = self.last_rec
+            self.head_btc = self._conv([h], self._site("output_layer", out), stats=False)
+            self.head_rec = self.last_rec
 
     def forward(self, x, train: bool = False, dropout_seed: int = 0):
-        m, lib, B, T = self.m, self.lib, self.B, self.T
+        m, B, T = self.m, self.B, self.T
         if tuple(x.shape) != (B, m.in_channels, T):
             raise ValueError(f"plan was built for {(B, m.in_channels, T)}, got {tuple(x.shape)}")
         x = x.contiguous()
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         self.repack(stream)
         p = float(getattr(m, "dropout", 0.0)) if train else 0.0
-        for d in self.dropout_descs:
-            if p > 0.0:
-                d.flags |= TQ_CONV_DROPOUT
-                d.dropout_p, d.dropout_seed = p, dropout_seed
-            else:
-                d.flags &= ~TQ_CONV_DROPOUT
+        self._arm_dropout(p, dropout_seed)
         self._last = dict(x=x, train=train, dropout_p=p, dropout_seed=dropout_seed, block_kv=self._block_kv)
-        stem = m.input_layer
         trace = None if torch.cuda.is_current_stream_capturing() else self._trace   # (measurement only: HIP events around every launch)
-        ev = _recorded_event if trace is not None else None
-        e0 = ev() if ev else None
-        self._run_stem(x, None, stem, m.in_channels, stream, "input layer")
-        if ev:
-            if self.wide_stem:
-                trace.append(("nct_to_btc:input layer", 0, 4 * B * T * (m.in_channels + self.x_btc.C), e0, ev()))
-            else:
-                trace.append(("input layer", 2 * B * T * m.in_channels * stem.out_channels * stem.kernel_size[0],
-                              4 * B * T * (m.in_channels + stem.out_channels), e0, ev()))
-        for i, (fn, args, what, fl) in enumerate(self.ops):
-            a = ev() if ev else None
-            rc = fn(*args, stream)
-            if ev:
-                trace.append((what, fl, self.op_bytes[i], a, ev()))
-            if rc:
-                check(rc, what)
-        out = m.output_layer
-        e0 = ev() if ev else None
-        if self.out_mode == "head":
-            check(lib.tq_head_conv_fwd(_p(self.final.buf), None, None, _p(out.weight), _p(out.bias), None, None, None,
-                                       _p(self.out_nct), B, self.final.T, self.final.C, out.out_channels, out.kernel_size[0],
-                                       stream), "output layer")
-        else:
-            self.out_nct.copy_(self.out_btc.buf.permute(0, 2, 1))  # (B,T,C) -> (B,C,T): 1/60 of the encoder's traffic
-        if ev:
-            trace.append(("output layer" if self.out_mode == "head" else "output layout flip", 2 * B * self.final.T * self.final.C * out.out_channels
-                          * out.kernel_size[0] if self.out_mode == "head" else 0, 4 * B * self.final.T * (self.final.C + out.out_channels), e0, ev()))
+        self._run_stem(x, None, m.input_layer, m.in_channels, stream, trace, "input layer", "input layer")
+        self._run_ops(self.ops, stream, trace)
+        self._fwd_count += 1
+        self._run_head(m.output_layer, None, stream, trace, "output layer", "output layer")
         self._mark_use(stream)
         return self.out_nct
 

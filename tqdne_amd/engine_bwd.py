@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import (PACK_MODE_T, TQ_AMAX_WORDS, TQ_BWD_ACCUM, TQ_BWD_DROPOUT, TQ_BWD_GN, TQ_BWD_SILU, TQ_BWD_STATS, TQ_WFMT_BF16X3, TQ_WFMT_F16_MX6, STAT_SLOT,
-                   TqConvBwdDesc, check)
+                   TqConvBwdDesc, TqConvDesc, check)
 
 
 TAIL_WORDS = 2   # floats reserved behind the parameter gradients in a backward plan's flat buffer (see BackwardPlan.run, tail_fill)
@@ -68,9 +68,35 @@ class BackwardPlan:
         self._scratch: Dict = {}
         self.op_flops: Dict[int, int] = {}   # index into self.ops -> algorithmic FLOP of that launch (bench tables)
         self._trace = None                   # list: HIP-event pairs around every launch of the next sweeps (measurement only)
+        self._wgrad_ops = []                 # indices into self.ops of the launches that take the weight-gradient workspace
+        self.ws_bytes = 0                    # ... and the most any of them asks for
+        self._grad_writer = {}               # data_ptr of a gradient tensor -> (op entry of its last writer so far,)
+        self.head_op = self.stem_op = None   # launches with dynamic arguments in front of / behind the sweep
+        self.dx_op = None                    # the input layer's data gradient (built on first use, _input_gradient)
+        self.last_dx = None
+        self.wide_head = eng.wide_head
+        # the input layer as a generic conv over a channels-last input padded to the 32-channel granule: the forward's own (a stem of
+        # more than 16 signal channels already ran that way) or a copy made by the sweep
+        self.wide_stem = eng.wide_stem
+        self.stem_cp = eng.x_btc.C if eng.wide_stem else 32
+        self.stem_generic = False
+        self.stem_x_btc = self.dw_stem32 = None
+        self._side_evs = {}                  # index of a weight-gradient op -> the event that orders the side stream behind the sweep
+        self._fire_cache = None
+        self._gemm_levels = None             # job tables of the embedding backward (built on first use, _embedding_jobs)
         self._layout_gradients()
+        for a in eng.acts:
+            a.gw = False
         self._build()
+        self._finish_workspace()
         eng.enable_block_kv()   # (from the next forward on; this plan's first sweep still re-derives the planes)
+
+    def _finish_workspace(self):
+        """one workspace for the slabs of every weight-gradient launch (they run one after the other): argument slots 7 and 8"""
+        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.dev)
+        for i in self._wgrad_ops:
+            self.ops[i][1][7] = self.ws.data_ptr()
+            self.ops[i][1][8] = self.ws.numel()
 
     # ------------------------------------------------------------------ memory
     def _empty(self, *shape):
@@ -236,7 +262,7 @@ class BackwardPlan:
         ``dw``: destination (C_out, C_in, K) of the site's PADDED geometry where that differs from the parameter's (wide head)."""
         lib, site = self.lib, rec.site
         need = lib.tq_conv1d_bwd_weight_workspace(C.byref(rec.desc))
-        self.ws_bytes = max(getattr(self, "ws_bytes", 0), need)
+        self.ws_bytes = max(self.ws_bytes, need)
         self._wgrad_ops.append(len(self.ops))
         s0 = rec.srcs[0]
         s1 = rec.srcs[1] if len(rec.srcs) > 1 else None
@@ -286,7 +312,7 @@ class BackwardPlan:
         cin_ok = site.C_in % 128 == 0 or (site.C_in % 64 == 0 and DGRAD_MX6_C64)
         mx6 = (_lib.requested_scheme() == "f16mx6"
                and amax is not None and site.C_out % 64 == 0 and cin_ok
-               and getattr(self.e, "scheme", "auto") == "auto" and getattr(self.m, "_conv_scheme", "auto") == "auto")
+               and self.e.scheme == "auto" and getattr(self.m, "_conv_scheme", "auto") == "auto")
         want = 5 if mx6 else 1
         if site.packed_t is None:
             nb = max(lib.tq_conv_weight_pack_bytes(site.C_out, site.C_in, site.K, 1),
@@ -320,7 +346,7 @@ class BackwardPlan:
             if rec.silu:
                 f |= TQ_BWD_SILU
             if rec.dropout:
-                self.bwd_dropout_descs.append((d, rec.desc))
+                self.bwd_dropout_descs.append(d)
         d.flags = f
         d.dropout_site = rec.desc.dropout_site
         self._keep.append(d)
@@ -356,17 +382,10 @@ class BackwardPlan:
     # ------------------------------------------------------------------ plan
     def _build(self):
         e, m, lib, B = self.e, self.m, self.lib, self.B
-        self._wgrad_ops = []
-        self._grad_writer = {}   # data_ptr of a gradient tensor -> (op entry of its last writer so far,)
-        if not hasattr(e, "dgrad_sites"):
-            e.dgrad_sites = []
-        for a in e.acts:
-            a.gw = False
         # ---- head
         final = e.final
         head = m.out[2]
         from .engine import _check_head_bwd_limits
-        self.wide_head = bool(getattr(e, "wide_head", False))
         if not self.wide_head:
             _check_head_bwd_limits(final.C, m.out_channels, head.kernel_size[0])
         Gh = self.scratch("G", final.T, final.C)
@@ -389,7 +408,6 @@ class BackwardPlan:
         # ---- stem (dynamic: x, in_scale)
         stem = m.input_blocks[0][0]
         so = e.stem_out
-        assert so.gw
         self.stem_op = [lib.tq_stem_conv_bwd_weight_ws, [_p(so.grad), None, None, _p(self.g(stem.weight)), B, m.in_channels, so.T,
                                                          stem.out_channels, stem.kernel_size[0], _p(self._ws_stem), nws], "stem wgrad"]
         self._ready[id(stem.weight)] = self.END  # (run after the sweep, not from self.ops)
@@ -397,11 +415,15 @@ class BackwardPlan:
         # are differentiated as a generic fused conv over a (B, T, 32) channels-last copy of the pre-scaled input
         # ... and stems of more than 16 signal channels, whose forward already is that generic conv: the weight gradient reads the
         # padded channels-last input the forward's tq_nct_to_btc wrote (no copy)
-        self.wide_stem = bool(getattr(e, "wide_stem", False))
-        self.stem_cp = e.x_btc.C if self.wide_stem else 32
-        self.stem_generic = self.wide_stem or stem.out_channels * m.in_channels * stem.kernel_size[0] > 2048
-        if self.stem_generic:
-            from ._lib import TqConvDesc
+        self._stem_gradients(stem, self.wide_stem or stem.out_channels * m.in_channels * stem.kernel_size[0] > 2048, "wgrad:stem (generic)")
+
+    def _stem_gradients(self, stem, generic: bool, what: str):
+        """The last ops of the sweep: the input layer's weight gradient in its ``generic`` form -- a fused conv's, into ``dw_stem32``
+        in the padded geometry; the run copies the real rows out -- and its bias gradient (column sums)."""
+        e, lib, B, so = self.e, self.lib, self.B, self.e.stem_out
+        assert so.gw
+        self.stem_generic = generic
+        if generic:
             K, Cp = stem.kernel_size[0], self.stem_cp
             if self.wide_stem:
                 self.stem_x_btc = e.x_btc.buf
@@ -413,16 +435,11 @@ class BackwardPlan:
             d.ktaps, d.stride, d.pad, d.upsample, d.flags = K, 1, K // 2, 0, 0
             self._keep.append(d)
             self.dw_stem32 = self._empty(stem.out_channels, Cp, K)
-            self.ws_bytes = max(getattr(self, "ws_bytes", 0), lib.tq_conv1d_bwd_weight_workspace(C.byref(d)))
+            self.ws_bytes = max(self.ws_bytes, lib.tq_conv1d_bwd_weight_workspace(C.byref(d)))
             self._wgrad_ops.append(len(self.ops))
             self.ops.append([lib.tq_conv1d_bwd_weight, [C.byref(d), _p(so.grad), _p(self.stem_x_btc), None, None, None,
-                                                        _p(self.dw_stem32), None, 0], "wgrad:stem (generic)"])
+                                                        _p(self.dw_stem32), None, 0], what])
         self.ops.append([lib.tq_colsum, [_p(so.grad), B, so.T, so.C, None, 0, _p(self.g(stem.bias)), None, None, None], "colsum:stem"])
-        # shared workspace of the weight-gradient slabs
-        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.dev)
-        for i in self._wgrad_ops:
-            self.ops[i][1][7] = self.ws.data_ptr()
-            self.ops[i][1][8] = self.ws.numel()
 
     def _wide_head_bwd(self, rec, head, final, Gh, co):
         """Backward of a head with 17 ... 64 output channels (engine._wide_head: a generic conv site padded to the 32-channel granule):
@@ -548,7 +565,6 @@ class BackwardPlan:
           bias:    column sums of d out over the real (B, 2T, C) view (+ its max|.| for the fp16-range data gradient)
           weights: k = 3 weight gradient d W2 (2C, C_in, 3), folded onto the five taps (tq_upsample_poly_wgrad_fold)
           input:   k = 3 data gradient with the transposed two-phase weights, written (or accumulated) straight into d x"""
-        from ._lib import TqConvDesc
         from .engine import ConvRec
         lib = self.lib
         x, out, rec = t["x"], t["out"], t["rec"]
@@ -562,7 +578,7 @@ class BackwardPlan:
         dw.ktaps, dw.stride, dw.pad, dw.upsample, dw.flags = 3, 1, 1, 0, 0
         self._keep.append(dw)
         dW2 = self._empty(2 * site.C_out, site.C_in, 3)
-        self.ws_bytes = max(getattr(self, "ws_bytes", 0), lib.tq_conv1d_bwd_weight_workspace(C.byref(dw)))
+        self.ws_bytes = max(self.ws_bytes, lib.tq_conv1d_bwd_weight_workspace(C.byref(dw)))
         self._wgrad_ops.append(len(self.ops))
         self.op_flops[len(self.ops)] = 2 * site.C_in * 2 * site.C_out * 3 * x.T * self.B
         self.ops.append([lib.tq_conv1d_bwd_weight_colsum, [C.byref(dw), _p(dout), _p(x.buf), None, None, None, _p(dW2), None, 0,
@@ -575,7 +591,7 @@ class BackwardPlan:
         x.gw = True
 
     def _bwd_up(self, t):
-        if getattr(t["rec"], "poly", None) is not None:
+        if t["rec"].poly is not None:
             return self._bwd_up_poly(t)
         x, out, rec = t["x"], t["out"], t["rec"]
         assert out.gw
@@ -604,41 +620,97 @@ class BackwardPlan:
         x.gw = True
 
     # ------------------------------------------------------------------ run
-    def _input_gradient(self, last, stream):
-        """d loss / d x (B, C_in, T) of the last forward: the stem conv's data gradient (reference: plain autograd through
-        ``input_blocks[0]``, unet.py:233,389-391), as a generic transposed conv of d stem_out into a 32-channel channels-last buffer
-        (the packer zero-fills the weight rows of the channels the model does not have), times the per-sample input scale where
-        the stem load applied one (EDM's c_in).  Built on first use: training never asks for it."""
-        e, m, lib = self.e, self.m, self.lib
-        stem, so = m.input_blocks[0][0], e.stem_out
+    def _input_gradient(self, stem, stream, what: str, in_scale=None, c0=None):
+        """d loss / d x (B, C_in, T) of the last forward: the input conv's data gradient (reference: plain autograd through
+        ``input_blocks[0]``, unet.py:233,389-391), as a generic transposed conv of d stem_out into a channels-last buffer padded to the
+        32-channel granule (the packer zero-fills the weight rows of the channels the model does not have), times the per-sample input
+        scale where the stem load applied one (EDM's c_in; None for an Encoder / Decoder).  ``c0``: the leading channels that were the
+        forward's ``x`` (default: all).  Built on first use: training never asks for it."""
+        lib, so = self.lib, self.e.stem_out
         cin, K = stem.in_channels, stem.kernel_size[0]
         Cp = self.stem_cp
         if cin > Cp:
             raise NotImplementedError(f"input gradient for more than {Cp} input channels")
-        if getattr(self, "dx_op", None) is None:
+        if self.dx_op is None:
             self.dx_btc = self._empty(self.B, so.T, Cp)
             self.stem_packed_t = torch.empty(lib.tq_conv_weight_pack_bytes(stem.out_channels, cin, K, 1), dtype=torch.uint8, device=self.dev)
             bd = TqConvBwdDesc()
             bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = self.B, so.T, stem.out_channels, Cp, 0, K, 0
             self._keep.append(bd)
             self.dx_op = [lib.tq_conv1d_bwd_data, [C.byref(bd), _p(so.grad), _p(self.stem_packed_t), None, None, None, None,
-                                                   _p(self.dx_btc), None, None], "dgrad:stem"]
+                                                   _p(self.dx_btc), None, None], "dgrad:" + what]
         check(lib.tq_pack_conv_weight(stem.weight.data_ptr(), stem.out_channels, cin, K, 1, self.stem_packed_t.data_ptr(), stream),
-              "pack^T stem")
-        fn, args, what = self.dx_op
-        check(fn(*args, stream), what)
+              "pack^T " + what)
+        fn, args, name = self.dx_op
+        check(fn(*args, stream), name)
         if self.wide_stem:
             # layout change, the input scale and the choice of the channels that were the forward's ``x`` in one launch (a conditioning
             # signal concatenated by the stem sits behind them and gets no gradient: the window starts at channel 0)
-            c0 = last.get("c0", cin)
+            c0 = cin if c0 is None else c0
             dx = torch.empty(self.B, c0, so.T, dtype=torch.float32, device=self.dev)   # (a fresh tensor: autograd may keep it)
-            check(lib.tq_btc_to_nct(_p(self.dx_btc), _p(last["in_scale"]), None, None, _p(dx), self.B, so.T, Cp, 0, c0, stream),
+            check(lib.tq_btc_to_nct(_p(self.dx_btc), _p(in_scale), None, None, _p(dx), self.B, so.T, Cp, 0, c0, stream),
                   "input gradient (btc_to_nct)")
             return dx
         dx = self.dx_btc[:, :, :cin].permute(0, 2, 1).contiguous()
-        if last["in_scale"] is not None:
-            dx.mul_(last["in_scale"][:, None, None])
+        if in_scale is not None:
+            dx.mul_(in_scale[:, None, None])
         return dx
+
+    def _begin_run(self, stream):
+        """what every sweep starts with: the data gradients' scheme and weights, a zeroed flat buffer, the dropout of the last forward"""
+        last = self.e._last
+        self._follow_scheme()
+        self.e.repack_transposed(stream)
+        self.flat.zero_()
+        self.e._arm_dropout(float(last["dropout_p"]), int(last["dropout_seed"]), self.bwd_dropout_descs, TQ_BWD_DROPOUT)
+        return last
+
+    def _sweep(self, stream, side=None, fire=None, on_bucket=None, trace=None):
+        """The launches of ``self.ops``, in order.  ``side``: a second stream for the weight gradients; ``fire``: {op index: [(lo, hi)]}
+        slices of the flat buffer to hand to ``on_bucket`` behind that op; ``trace``: a list that gets HIP events around every launch."""
+        if side is None and not fire and trace is None:
+            for fn, args, what in self.ops:
+                rc = fn(*args, stream)
+                if rc:
+                    check(rc, what)
+            return
+        from .engine import _recorded_event
+        main_t = torch.cuda.current_stream(self.dev)
+        fire = fire or {}
+        for i, (fn, args, what) in enumerate(self.ops):
+            on = stream
+            if side is not None:
+                if what.startswith("recompute:"):   # (use_checkpoint: shared block-internal buffers are about to be overwritten)
+                    main_t.wait_stream(side)
+                elif what.startswith("wgrad:"):   # (the column sums on that stream too: measured equal)
+                    ev = self._side_evs.get(i)
+                    if ev is None:
+                        ev = self._side_evs[i] = torch.cuda.Event()
+                    ev.record(main_t)
+                    side.wait_event(ev)
+                    on = side.cuda_stream
+            a = _recorded_event() if trace is not None else None
+            rc = fn(*args, on)
+            if trace is not None:
+                trace.append((what, self.op_flops.get(i, 0), 0, a, _recorded_event()))
+            if rc:
+                check(rc, what)
+            if i in fire:
+                if side is not None:
+                    main_t.wait_stream(side)   # (the exchange waits on the main stream only)
+                for lo, hi in fire[i]:
+                    on_bucket(self.flat[lo:hi])
+        if side is not None:
+            main_t.wait_stream(side)
+
+    def _results(self, clone: bool):
+        """the gradients as a list aligned with ``model.parameters()`` (None for frozen parameters)"""
+        out = self.flat.clone() if clone else self.flat  # clone: autograd may keep the returned tensors alive
+        res = []
+        for p_ in self.param_order:
+            o = self.offs[id(p_)]
+            res.append(out[o:o + p_.numel()].view_as(p_) if p_.requires_grad else None)
+        return res
 
     def run(self, dpred: torch.Tensor, gloss: torch.Tensor, clone: bool = True, on_bucket=None, bucket_elems: int = 4 << 20,
              tail_fill=None, want_dx: bool = False):
@@ -659,21 +731,11 @@ class BackwardPlan:
                     tail_fill(flat[n_grad:n_grad + TAIL_WORDS])
                     sl = flat[sl.storage_offset():n_grad + TAIL_WORDS]
                 user_bucket(sl)
-        e, m, lib = self.e, self.m, self.lib
-        last = e._last
-        if last.get("infer", False):
+        e, m = self.e, self.m
+        if e._last.get("infer", False):
             raise RuntimeError("the last forward of this plan was an inference forward (infer=True): it kept nothing for a backward")
         stream = torch.cuda.current_stream(self.dev).cuda_stream
-        self._follow_scheme()
-        e.repack_transposed(stream)
-        self.flat.zero_()
-        p, seed = float(last["dropout_p"]), int(last["dropout_seed"])
-        for d, fd in self.bwd_dropout_descs:
-            if p > 0.0:
-                d.flags |= TQ_BWD_DROPOUT
-                d.dropout_p, d.dropout_seed = p, seed
-            else:
-                d.flags &= ~TQ_BWD_DROPOUT
+        last = self._begin_run(stream)
         c_out = last["c_out"]
         gl = gloss.to(torch.float32).reshape(())
         cs = (c_out * gl) if c_out is not None else gl.expand(self.B).contiguous()
@@ -681,70 +743,22 @@ class BackwardPlan:
         fn, args, what = self.head_op
         args[0], args[1] = dpred.data_ptr(), cs.data_ptr()
         check(fn(*args, stream), what)
-        cin = m.in_channels
+        stem, cin = m.input_blocks[0][0], m.in_channels
         if self.stem_generic and not self.wide_stem:
             xs = last["x"] if last["in_scale"] is None else last["x"] * last["in_scale"][:, None, None]
             self.stem_x_btc[:, :, :cin].copy_(xs.permute(0, 2, 1))
-        if self._trace is not None:
-            from .engine import _recorded_event
-            # (a traced pass still hands every bucket to the gradient exchange: a trainer that traces must not step on
-            # un-reduced gradients)
-            fire, late = self._fire_points(bucket_elems) if on_bucket is not None else ({}, ())
-            for i, (fn, args, what) in enumerate(self.ops):
-                a = _recorded_event()
-                rc = fn(*args, stream)
-                self._trace.append((what, self.op_flops.get(i, 0), 0, a, _recorded_event()))
-                if rc:
-                    check(rc, what)
-                if i in fire:
-                    for lo, hi in fire[i]:
-                        on_bucket(self.flat[lo:hi])
-        elif BWD_STREAMS == 2:
+        # (a traced pass still hands every bucket to the gradient exchange: a trainer that traces must not step on un-reduced gradients)
+        fire, late = self._fire_points(bucket_elems) if on_bucket is not None else ({}, ())
+        side = None
+        if self._trace is None and BWD_STREAMS == 2:
             # Weight gradients on a second stream: they only read (dy, forward activations) and write their own slice of the
             # flat buffer, so the sweep's chain (data gradients, GroupNorm backward, column sums: half of it HBM-bound) does not
             # have to wait for them.  Every gradient tensor a weight-gradient launch reads is a buffer of its own, never reused.
-            main_t = torch.cuda.current_stream(self.dev)
             from .engine import side_stream
             side = side_stream(self.dev, 1)   # (the sampler lanes' pool: a stream of its own would be one hardware queue too many)
-            if self.__dict__.get("_side_evs") is None:
-                self._side_evs = {}
-            fire, late = self._fire_points(bucket_elems) if on_bucket is not None else ({}, ())
-            for i, (fn, args, what) in enumerate(self.ops):
-                if what.startswith("recompute:"):   # (use_checkpoint: shared block-internal buffers are about to be overwritten)
-                    main_t.wait_stream(side)
-                if what.startswith("wgrad:"):   # (the column sums on that stream too: measured equal)
-                    ev = self._side_evs.get(i)
-                    if ev is None:
-                        ev = self._side_evs[i] = torch.cuda.Event()
-                    ev.record(main_t)
-                    side.wait_event(ev)
-                    rc = fn(*args, side.cuda_stream)
-                else:
-                    rc = fn(*args, stream)
-                if rc:
-                    check(rc, what)
-                if i in fire:
-                    main_t.wait_stream(side)   # (the exchange waits on the main stream only)
-                    for lo, hi in fire[i]:
-                        on_bucket(self.flat[lo:hi])
-            main_t.wait_stream(side)
-        elif on_bucket is None:
-            for fn, args, what in self.ops:
-                rc = fn(*args, stream)
-                if rc:
-                    check(rc, what)
-            late = ()
-        else:
-            fire, late = self._fire_points(bucket_elems)
-            for i, (fn, args, what) in enumerate(self.ops):
-                rc = fn(*args, stream)
-                if rc:
-                    check(rc, what)
-                if i in fire:
-                    for lo, hi in fire[i]:
-                        on_bucket(self.flat[lo:hi])
+        self._sweep(stream, side, fire, on_bucket, self._trace)
         if self.stem_generic:
-            self.gv(m.input_blocks[0][0].weight).copy_(self.dw_stem32[:, :cin, :])
+            self.gv(stem.weight).copy_(self.dw_stem32[:, :cin, :])
         else:
             fn, args, what = self.stem_op
             args[1], args[2] = last["x"].data_ptr(), _p(last["in_scale"])
@@ -752,16 +766,8 @@ class BackwardPlan:
         self._embedding_backward(last)
         for lo, hi in late:
             on_bucket(self.flat[lo:hi])
-        self.last_dx = self._input_gradient(last, stream) if want_dx else None
-        out = self.flat.clone() if clone else self.flat  # clone: autograd may keep the returned tensors alive
-        res = []
-        for p_ in self.param_order:
-            if not p_.requires_grad:
-                res.append(None)
-            else:
-                o = self.offs[id(p_)]
-                res.append(out[o:o + p_.numel()].view_as(p_))
-        return res
+        self.last_dx = self._input_gradient(stem, stream, "stem", last["in_scale"], last.get("c0")) if want_dx else None
+        return self._results(clone)
 
     def _follow_scheme(self):
         """the forward plan left the fp16-range scheme (range guard, or bf16x3 on request): the data gradients follow -- descriptors
@@ -774,7 +780,7 @@ class BackwardPlan:
 
     def _fire_points(self, bucket_elems):
         key = int(bucket_elems)
-        cached = getattr(self, "_fire_cache", None)
+        cached = self._fire_cache
         if cached is None or cached[0] != key:
             fire, late = {}, []
             for lo, hi, r in self.plan_buckets(key):
@@ -858,7 +864,7 @@ class BackwardPlan:
         """Backward of Fourier -> time MLP (+ cond MLP) -> per-block Linear(SiLU(emb)) (unet.py:91-97, 210-227, 383-388): the
         Fourier features and three tq_gemm_f32_jobs launches (see _embedding_jobs)."""
         e, m, lib = self.e, self.m, self.lib
-        if getattr(self, "_gemm_levels", None) is None:
+        if self._gemm_levels is None:
             self._embedding_jobs()
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         check(lib.tq_fourier_features(_p(last["timesteps"]), _p(m.time_embed.W), _p(self.four), self.B, m.model_channels // 2, stream),
@@ -876,15 +882,8 @@ class SeqBackwardPlan(BackwardPlan):
     channels-last copy of the input padded to 32 channels (the packer zero-fills the missing weight rows / k entries)."""
 
     def _build(self):
-        from ._lib import TqConvDesc
-        from .engine import Act, ConvRec, ConvSite, _check_head_bwd_limits
+        from .engine import _check_head_bwd_limits
         e, m, lib, B = self.e, self.m, self.lib, self.B
-        self._wgrad_ops = []
-        self._grad_writer = {}   # data_ptr of a gradient tensor -> (op entry of its last writer so far,)
-        if not hasattr(e, "dgrad_sites"):
-            e.dgrad_sites = []
-        for a in e.acts:
-            a.gw = False
         final, out = e.final, m.output_layer
         dfin = self.grad(final)
         if e.out_mode == "head":   # narrow output (decoder): VALU kernel straight from the NCW gradient
@@ -896,104 +895,31 @@ class SeqBackwardPlan(BackwardPlan):
                                                       out.out_channels, out.kernel_size[0], _p(self._ws_head), nws], "output layer bwd"]
             self.dout_btc = None
         else:                      # wide output (encoder): generic conv gradients from a channels-last copy of d out
-            self.head_op = None
             self.dout_btc = self._empty(B, final.T, out.out_channels)
-            self._wgrad(e.out_rec, self.dout_btc)
-            self._dgrad(e.out_rec, self.dout_btc, final.T, [dfin], accumulate=False, chain=False)
+            self._wgrad(e.head_rec, self.dout_btc)
+            self._dgrad(e.head_rec, self.dout_btc, final.T, [dfin], accumulate=False, chain=False)
         final.gw = True
         for kind, t in reversed(e.tape):
             getattr(self, "_bwd_" + kind)(t)
-        # ---- input layer: generic conv over a (B, T, 32) channels-last copy of the input
-        stem, so = m.input_layer, e.stem_out
-        assert so.gw
-        cin, K = stem.in_channels, stem.kernel_size[0]
-        # (an input layer of more than 16 channels already ran as that generic conv: its padded channels-last input is the forward's)
-        self.wide_stem = bool(getattr(e, "wide_stem", False))
-        Cp = self.stem_cp = e.x_btc.C if self.wide_stem else 32
-        if self.wide_stem:
-            self.x_btc = e.x_btc
-        else:
-            self.x_btc = Act(self._empty(B, so.T, Cp), None, Cp, so.T)
-            self.x_btc.buf.zero_()
-        site = ConvSite("input_layer", stem.weight, stem.bias, self.dev, lib)
-        site.C_in = Cp  # descriptor / packed geometry see the padded input; pack kernels guard the real (C_out, cin, K) weight
-        d = TqConvDesc()
-        d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, so.T, so.T, Cp, 0, stem.out_channels
-        d.ktaps, d.stride, d.pad, d.upsample, d.flags = K, 1, K // 2, 0, 0
-        self._keep.append(d)
-        rec = ConvRec(site, d, [self.x_btc], None, so, 1, False, False, False)
-        self.dw_stem32 = self._empty(stem.out_channels, Cp, K)
-        need = lib.tq_conv1d_bwd_weight_workspace(C.byref(d))
-        self.ws_bytes = max(getattr(self, "ws_bytes", 0), need)
-        self._wgrad_ops.append(len(self.ops))
-        self.ops.append([lib.tq_conv1d_bwd_weight, [C.byref(d), _p(so.grad), _p(self.x_btc.buf), None, None, None,
-                                                    _p(self.dw_stem32), None, 0], "wgrad:input_layer"])
-        self.ops.append([lib.tq_colsum, [_p(so.grad), B, so.T, so.C, None, 0, _p(self.g(stem.bias)), None, None, None], "colsum:stem"])
-        # d input (only run on request): transposed conv into a 32-channel channels-last buffer
-        self.dx_btc = self._empty(B, so.T, Cp)
-        n0 = len(self.ops)
-        site.packed_t = torch.empty(lib.tq_conv_weight_pack_bytes(stem.out_channels, cin, K, 1), dtype=torch.uint8, device=self.dev)
-        self.stem_site = site
-        bd = TqConvBwdDesc()
-        bd.B, bd.T, bd.C_dy, bd.C_dx0, bd.C_dx1, bd.ktaps, bd.flags = B, so.T, stem.out_channels, Cp, 0, K, 0
-        self._keep.append(bd)
-        self.dx_op = [lib.tq_conv1d_bwd_data, [C.byref(bd), _p(so.grad), _p(site.packed_t), None, None, None, None,
-                                               _p(self.dx_btc), None, None], "dgrad:input_layer"]
-        assert len(self.ops) == n0
-        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.dev)
-        for i in self._wgrad_ops:
-            self.ops[i][1][7] = self.ws.data_ptr()
-            self.ops[i][1][8] = self.ws.numel()
+        # (an input layer of more than 16 channels already ran as the generic conv: its padded channels-last input is the forward's)
+        self._stem_gradients(m.input_layer, True, "wgrad:input_layer")
 
     def run_seq(self, dout: torch.Tensor, want_dx: bool = False, clone: bool = True):
-        e, m, lib = self.e, self.m, self.lib
-        last = e._last
+        m = self.m
         stream = torch.cuda.current_stream(self.dev).cuda_stream
-        self._follow_scheme()
-        e.repack_transposed(stream)
+        last = self._begin_run(stream)
         stem = m.input_layer
-        cin, K = stem.in_channels, stem.kernel_size[0]
-        if want_dx:
-            check(lib.tq_pack_conv_weight(stem.weight.data_ptr(), stem.out_channels, cin, K, 1, self.stem_site.packed_t.data_ptr(),
-                                          stream), "pack^T input_layer")
-        self.flat.zero_()
-        p, seed = float(last["dropout_p"]), int(last["dropout_seed"])
-        for d, fd in self.bwd_dropout_descs:
-            if p > 0.0:
-                d.flags |= TQ_BWD_DROPOUT
-                d.dropout_p, d.dropout_seed = p, seed
-            else:
-                d.flags &= ~TQ_BWD_DROPOUT
+        cin = stem.in_channels
         dout = dout.contiguous()
         if not self.wide_stem:
-            self.x_btc.buf[:, :, :cin].copy_(last["x"].permute(0, 2, 1))
+            self.stem_x_btc[:, :, :cin].copy_(last["x"].permute(0, 2, 1))
         if self.head_op is not None:
             fn, args, what = self.head_op
             args[0] = dout.data_ptr()
             check(fn(*args, stream), what)
         else:
             self.dout_btc.copy_(dout.permute(0, 2, 1))
-        for fn, args, what in self.ops:
-            rc = fn(*args, stream)
-            if rc:
-                check(rc, what)
+        self._sweep(stream)   # (every launch on the one stream)
         self.gv(stem.weight).copy_(self.dw_stem32[:, :cin, :])
-        dx = None
-        if want_dx:
-            fn, args, what = self.dx_op
-            check(fn(*args, stream), what)
-            if self.wide_stem:
-                dx = torch.empty(self.B, cin, e.stem_out.T, dtype=torch.float32, device=self.dev)
-                check(lib.tq_btc_to_nct(_p(self.dx_btc), None, None, None, _p(dx), self.B, e.stem_out.T, self.stem_cp, 0, cin, stream),
-                      "input gradient (btc_to_nct)")
-            else:
-                dx = self.dx_btc[:, :, :cin].permute(0, 2, 1).contiguous()
-        out = self.flat.clone() if clone else self.flat
-        res = []
-        for p_ in self.param_order:
-            if not p_.requires_grad:
-                res.append(None)
-            else:
-                o = self.offs[id(p_)]
-                res.append(out[o:o + p_.numel()].view_as(p_))
-        return res, dx
+        dx = self._input_gradient(stem, stream, "input_layer") if want_dx else None
+        return self._results(clone), dx
