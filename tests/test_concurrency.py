@@ -65,12 +65,8 @@ def test_four_plans_on_four_streams_match_a_plan_alone():
     streams = [torch.cuda.current_stream(dev())] + [torch.cuda.Stream(dev()) for _ in range(L - 1)]
 
     def fwd(lane):
-        edm._lane = lane
-        try:
-            with torch.no_grad():
-                return edm._denoise_static(x, sig, 1, cond, infer=True)
-        finally:
-            edm._lane = 0
+        with torch.no_grad():
+            return edm._denoise_static(x, sig, 1, cond, infer=True, lane=lane)
 
     def tensors(eng):
         # (inference plans write only the q third of a qkv buffer: K and V go straight to the attention kernel's bf16 planes)

@@ -133,3 +133,63 @@ def test_edm_forward_input_gradient(concat):
     worst, wname, n = _compare_param_grads(edm.unet.named_parameters(), params, prefix="unet.")
     print(f"EDM forward, concat={concat}: d/dx {ex:.2e}; {n} parameter gradients, worst {worst:.2e} ({wname})")
     assert ex < TOL and worst < TOL
+
+
+class _CountingLib:
+    """the loaded library with every call into it counted (each entry point is wrapped once: the plans compare entry points by identity)"""
+
+    def __init__(self, lib):
+        self._lib, self._fns, self.calls = lib, {}, 0
+
+    def __getattr__(self, name):
+        fn = self._fns.get(name)
+        if fn is None:
+            real = getattr(self._lib, name)
+
+            def fn(*a):
+                self.calls += 1
+                return real(*a)
+            self._fns[name] = fn
+        return fn
+
+
+@pytest.mark.parametrize("bridge", ["edm_loss", "edm_forward", "unet", "ict_step", "ddpm_step"])
+def test_backward_of_an_overwritten_forward_is_refused_before_any_launch(bridge, monkeypatch):
+    """two forwards of one shape, then backward() of the FIRST: every autograd bridge refuses with the same message, before any call into
+    the library (the plan's static buffers hold the second forward's activations); the second's backward then runs as usual"""
+    from tqdne_amd import (DDPMScheduler, LightningDDMP, LightningEDM, LithningConsistencyModel, UNetModel, _lib,
+                           tiny_1d_unet_config)
+    lib = _CountingLib(_lib.load())
+    monkeypatch.setattr(_lib, "_LIB", lib)   # (before any plan of the models below is built)
+    cfg, opt = tiny_1d_unet_config(), {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0}
+    torch.manual_seed(0)
+    g = torch.Generator().manual_seed(47)
+    B, T = 2, 256
+    x, noise = torch.randn(B, 3, T, generator=g).to(dev()), torch.randn(B, 3, T, generator=g).to(dev())
+    eps, sigma = torch.randn(B, generator=g).to(dev()), torch.tensor([0.3, 7.0], device=dev())
+    if bridge == "edm_loss":
+        m = LightningEDM(cfg, opt).to(dev()).train()
+        f = lambda: m.step_with_noise(x, eps, noise)
+    elif bridge == "edm_forward":
+        m = LightningEDM(cfg, opt).to(dev()).train()
+        f = lambda: (m(x.clone().requires_grad_(True), sigma) * noise).sum()   # (a fresh model's output layer is zero: not its square)
+    elif bridge == "unet":
+        m = UNetModel(**cfg).to(dev()).train()
+        f = lambda: (m(x.clone().requires_grad_(True), sigma) * noise).sum()   # (a fresh model's output layer is zero: not its square)
+    elif bridge == "ict_step":
+        m = LithningConsistencyModel(UNetModel(**cfg)).to(dev()).train()
+        m.max_steps = 1000   # (no trainer: the iCT schedule reads the module's own attribute)
+        f = lambda: m.step({"signal": x})
+    else:
+        m = LightningDDMP(UNetModel(**cfg), DDPMScheduler(), opt).to(dev()).train()
+        f = lambda: m.step_with_noise({"signal": x}, noise, torch.tensor([10, 700], device=dev()))
+    first, second = f(), f()
+    calls = lib.calls
+    with pytest.raises(RuntimeError, match="another forward"):
+        first.backward()
+    assert lib.calls == calls, "the refused backward called into the library"
+    assert all(p.grad is None for p in m.parameters())
+    second.backward()
+    assert lib.calls > calls
+    grads = [p.grad for p in m.parameters() if p.grad is not None]
+    assert grads and all(bool(torch.isfinite(g_).all()) for g_ in grads) and any(float(g_.abs().max()) > 0 for g_ in grads)

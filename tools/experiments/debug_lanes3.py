@@ -40,11 +40,8 @@ def snapshot(eng):
 
 
 def fwd(lane):
-    edm._lane = lane
     with torch.no_grad():
-        y = edm._denoise_static(x, sig, 1, cond, infer=True)
-    edm._lane = 0
-    return y
+        return edm._denoise_static(x, sig, 1, cond, infer=True, lane=lane)
 
 # reference: each lane alone
 ref = []

@@ -16,10 +16,8 @@ x = (3.0 * torch.randn(h, 3, T, generator=g)).to(dev)
 cond = torch.randn(h, 5, generator=g).to(dev)
 sig = torch.full((h,), 2.0, device=dev)
 for lane in (0, 1):
-    edm._lane = lane
     with torch.no_grad():
-        edm._denoise_static(x, sig, 1, cond, infer=True)
-edm._lane = 0
+        edm._denoise_static(x, sig, 1, cond, infer=True, lane=lane)
 torch.cuda.synchronize()
 lib = _lib.load()
 e0, e1 = edm.unet._engine(h, T, dev, 0), edm.unet._engine(h, T, dev, 1)

@@ -4,6 +4,7 @@ must leave every launch, argument and order as it was).
     python tools/plan_listing.py LISTING.txt [OUTPUTS.pt]          (needs a GPU; run it from each tree against the SAME library build,
     python tools/plan_listing.py --diff OLD.txt NEW.txt             TQDNE_HIP_LIB=<path to libtqdne_hip.so>; then compare the two files)
     python tools/plan_listing.py --equal OLD.pt NEW.pt             (the inference outputs of every case, torch.equal)
+    python tools/plan_listing.py --models LISTING.txt [OUTPUTS.pt] (the layer ABOVE the plans, see below; same --diff / --equal)
 
 ``--diff`` is a line diff that lets ONE kind of line move within its run: the transposed pack of an input layer's weights for the input
 gradient (tq_pack_conv_weight mode 1), which only has to precede that gradient's launch: such lines are compared at the end of the run
@@ -15,10 +16,18 @@ the forward -- the dynamic stem / head launches among them -- the backward plan'
 ``dx_op``, and every call into the library made by each of those runs, in order, with the descriptors as they were armed at that moment.
 Integers and floats are written as they are, a device pointer as "buf<k>+<offset>" (resolved against the tensors the plan, its store,
 the model and the inputs hold; k counts first appearances within the case), a byref descriptor as its fields, a Python callable that
-stands in for a launch by its name.  The second process of a full check is the same run under TQDNE_GN_FOLD=1."""
+stands in for a launch by its name.  The second process of a full check is the same run under TQDNE_GN_FOLD=1.
+
+``--models`` lists what the model layer (edm.py, autograd.py, consistency_model.py, diffusion.py) makes of its public calls: per case and
+per call every library launch in order, with its stream (numbered by first appearance within the call) and its arguments resolved
+against everything the modules, their scratch caches, their plans and the inputs hold.  A device address that resolves to nothing held
+(a temporary of the call) is "tmp<k>", k by first appearance within the call.  torch.manual_seed(0) and rng.seed_rank(0) precede every
+case.  In OUTPUTS.pt the inference outputs and samples carry plain names (``--equal`` demands torch.equal); losses and gradients, which
+pass through the gradient kernels' atomics, carry a leading "~" (``--equal`` reports how many differ and the largest difference)."""
 
 import ctypes as C
 import difflib
+import gc
 import os
 import re
 import sys
@@ -36,6 +45,7 @@ class Recorder:
         self._lib, self._fns, self.log = lib, {}, None
         # launches: int status, the stream last (the size / limit queries a plan makes while it is built are not listed)
         self._launch = {n for n, (res, args) in protos.items() if res is C.c_int and len(args) > 1 and args[-1] is C.c_void_p}
+        self._ptr = {n: [t is C.c_void_p for t in args] for n, (res, args) in protos.items()}
 
     def __getattr__(self, name):
         fn = self._fns.get(name)
@@ -44,7 +54,8 @@ class Recorder:
 
             def fn(*a, _real=real, _name=name):
                 if self.log is not None and _name in self._launch:
-                    self.log.append((_name, [frozen(x) for x in a]))
+                    # (an address given as a number is marked as one; a byref descriptor under a void* parameter is copied out)
+                    self.log.append((_name, [("ptr", x) if p and isinstance(x, int) else frozen(x) for x, p in zip(a, self._ptr[_name])]))
                 return _real(*a)
             fn.__name__ = name
             self._fns[name] = fn
@@ -52,21 +63,27 @@ class Recorder:
 
 
 def frozen(a):
-    """an argument with every descriptor behind it copied out: int | float | None | ("struct", [(field, value)])"""
+    """an argument with every descriptor behind it copied out: int | float | None | ("ptr", address) | ("struct", [(field, value)])"""
     if hasattr(a, "_obj"):          # ctypes.byref(...)
         a = a._obj
     if isinstance(a, C.Structure):
-        return ("struct", [(f[0], frozen(getattr(a, f[0]))) for f in a._fields_])
+        return ("struct", [(f[0], ("ptr", getattr(a, f[0])) if f[1] is C.c_void_p else frozen(getattr(a, f[0]))) for f in a._fields_])
     if isinstance(a, C._Pointer):
         return frozen(a.contents) if a else None
     return a
 
 
+def stream_of(args):
+    s = args[-1]
+    return (s[1] if isinstance(s, tuple) else s) or 0
+
+
 class Names:
-    """device address -> "buf<k>+<offset>" against a set of storages; k in order of first appearance"""
+    """device address -> "buf<k>+<offset>" against a set of storages; k in order of first appearance.  ``tmp`` (a dict): an address
+    that is known to be one (an argument or descriptor field of pointer type) and lies in no storage is "tmp<k>" instead of a number."""
 
     def __init__(self):
-        self.ranges, self.k, self.seen = {}, {}, set()
+        self.ranges, self.k, self.seen, self.tmp = {}, {}, set(), None
 
     def gather(self, o, depth=0):
         if id(o) in self.seen or depth > 8:
@@ -92,14 +109,18 @@ class Names:
             for n in list(getattr(o, "__dict__", ())) + [s for c in type(o).__mro__ for s in getattr(c, "__slots__", ())]:
                 self.gather(getattr(o, n, None), depth + 1)
 
-    def arg(self, a):
+    def arg(self, a, ptr=False):
         if isinstance(a, tuple) and a and a[0] == "struct":
             return "{" + " ".join(f"{n}={self.arg(v)}" for n, v in a[1]) + "}"
+        if isinstance(a, tuple) and a and a[0] == "ptr":
+            return self.arg(a[1], True)
         if isinstance(a, int) and a >= 4096:
             for base, size in self.ranges.items():
                 if base <= a < base + max(size, 1):
                     k = self.k.setdefault(base, len(self.k))
                     return f"buf{k}+{a - base}"
+            if ptr and self.tmp is not None:
+                return f"tmp{self.tmp.setdefault(a, len(self.tmp))}"
         return repr(a)
 
     def call(self, fn, args):
@@ -208,7 +229,7 @@ def listing(out, outputs):
             out.write(f"-- calls: {tag}\n")
             streams = {}
             for name, args in log:
-                s = args[-1] or 0   # (every launch takes the stream last; the ones of this process in order of appearance)
+                s = stream_of(args)   # (every launch takes the stream last; the ones of this process in order of appearance)
                 out.write(f"     {names.call(name, args[:-1])} on stream {streams.setdefault(s, len(streams))}\n")
             return y
 
@@ -241,6 +262,198 @@ def listing(out, outputs):
         out.write(f"-- scheme={eng.scheme} wide_stem={eng.wide_stem} n_grad={b.n_grad}\n")
 
 
+def model_cases():
+    """(title, build() -> (modules, held, [(tag, call() -> {name: tensor to save})])) -- only names both sides of a refactor of the model
+    layer have: forward, step_with_noise, step_and_backward, sample_deterministically, sample_stochastically, sample_from,
+    LithningConsistencyModel.step, LightningDDMP.step_with_noise, autograd.edm_loss_and_grads"""
+    from tqdne_amd import DDPMScheduler, LightningDDMP, LightningEDM, LithningConsistencyModel, UNetModel, autograd, tiny_1d_unet_config
+    micro = dict(model_channels=32, channel_mult=(1, 2), num_res_blocks=1, attention_resolutions=(2,), num_heads=4, conv_kernel_size=5,
+                 dims=1, cond_features=5, dropout=0.1)
+    wide = dict(micro, in_channels=32, out_channels=16)          # 16 + 16 input channels: the wide stem concatenates the signal
+    tiny, narrow = tiny_1d_unet_config(), tiny_1d_unet_config(6, 3)   # narrow: 3 + 3 channels through tq_concat_scale
+    opt = {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0}
+    T = 256
+
+    def inputs(cfg, B, c1):
+        cond = rnd(4, B, cfg["cond_features"]) if cfg.get("cond_features") else None
+        return rnd(2, B, cfg["in_channels"] - c1, T), rnd(3, B).abs() + 0.1, (rnd(5, B, c1, T) if c1 else None), cond
+
+    def grads(m):
+        return torch.cat([p.grad.flatten() for p in m.parameters() if p.grad is not None])
+
+    def env(name, value, f):
+        def g():
+            os.environ[name] = value
+            try:
+                return f()
+            finally:
+                del os.environ[name]
+        return g
+
+    def edm(cfg, c1=0, B=2, train=False):
+        m = perturbed(LightningEDM(cfg, opt, num_sampling_steps=3), 1).train(train)
+        return (m,) + inputs(cfg, B, c1)
+
+    def edm_forward(cfg, c1):
+        def build():
+            m, x, sigma, cs, cond = edm(cfg, c1)
+
+            def call():
+                with torch.no_grad():
+                    return {"y": m(x, sigma, cs, cond)}
+            return [m], [x, sigma, cs, cond], [("forward under no_grad", call)]
+        return build
+
+    def edm_forward_grad(cfg, c1, train):
+        def build():
+            m, x, sigma, cs, cond = edm(cfg, c1, train=train)
+            G = rnd(9, *x.shape)
+
+            def call():
+                m.zero_grad(set_to_none=True)
+                xg = x.clone().requires_grad_(True)
+                y = m(xg, sigma, cs, cond)
+                (y * G).sum().backward()
+                return {"~y": y.detach(), "~dx": xg.grad, "~grads": grads(m)}
+            return [m], [x, sigma, cs, cond, G], [("forward with grad, backward", call)]
+        return build
+
+    def edm_step(cfg, c1, how, B=2, lanes=1):
+        def build():
+            m, x, _, cs, cond = edm(cfg, c1, B, train=True)
+            eps, noise = rnd(6, B), rnd(7, *x.shape)
+            batch = {k: v for k, v in (("signal", x), ("cond_signal", cs), ("cond", cond)) if v is not None}
+
+            def call():
+                m.zero_grad(set_to_none=True)
+                if how == "step_with_noise":
+                    loss = m.step_with_noise(x, eps, noise, cond=cond, cond_sample=cs)
+                    loss.backward()
+                elif how == "step_and_backward":
+                    loss, _ = m.step_and_backward(batch)
+                else:
+                    loss, _ = autograd.edm_loss_and_grads(m, x, eps, noise, cond, cs, lanes=lanes)
+                return {"~loss": loss.detach(), "~grads": grads(m)}
+            if how == "step_and_backward" and lanes > 1:
+                call = env("TQDNE_TRAIN_LANES", str(lanes), call)
+            return [m], [x, cs, cond, eps, noise], [(f"{how}, lanes={lanes}", call), (f"{how} again", call)]
+        return build
+
+    def edm_sample(cfg, c1, B, churn=False, repeat=1, **kw):
+        def build():
+            m, x, _, cs, cond = edm(cfg, c1, B)
+            sigmas = m.edm.sampling_sigmas(3).cuda()
+            start = (rnd(8, *x.shape).double() * sigmas[0]).contiguous()
+            if churn:
+                kw["churn_noises"] = [rnd(20 + i, *x.shape).double() for i in range(3)]
+            f = m.sample_stochastically if churn else m.sample_deterministically
+            call = lambda: {"sample": f(start, sigmas, cs, cond, **kw)}
+            return [m], [start, sigmas, cs, cond, kw], [(f"call {i}", call) for i in range(repeat)]
+        return build
+
+    def cm(cfg, c1, what, B=2):
+        def build():
+            m = perturbed(LithningConsistencyModel(UNetModel(**cfg)), 1)
+            x, sigma, cs, cond = inputs(cfg, B, c1)
+            us = [torch.rand(x.shape, generator=torch.Generator().manual_seed(30 + i)).cuda() for i in range(2)]
+
+            def forward():
+                with torch.no_grad():
+                    return {"y": m(x, sigma, cs, cond)}
+
+            def step():
+                m.zero_grad(set_to_none=True)
+                m.step({k: v for k, v in (("signal", x), ("cond_signal", cs), ("cond", cond)) if v is not None}).backward()
+                return {"~grads": grads(m)}
+            call = {"forward": forward, "lanes": env("TQDNE_CM_LANES", "2", forward), "step": step,
+                    "sample_from": lambda: {"sample": m.sample_from(x, [2.0, 0.5], us, cs, cond)}}[what]
+            m.train(what == "step")
+            m.max_steps = 1000   # (no trainer: the iCT schedule reads the module's own attribute)
+            return [m], [x, sigma, cs, cond, us], [(what, call)]
+        return build
+
+    def ddpm(cfg, c1):
+        def build():
+            m = perturbed(LightningDDMP(UNetModel(**cfg), DDPMScheduler(), opt, cond_signal_input=bool(c1)), 1).train()
+            x, _, cs, _ = inputs(cfg, 2, c1)
+            noise, t = rnd(7, *x.shape), torch.tensor([10, 700]).cuda()
+
+            def call():
+                m.zero_grad(set_to_none=True)
+                loss = m.step_with_noise({"signal": x, "cond_signal": cs}, noise, t)
+                loss.backward()
+                return {"~loss": loss.detach(), "~grads": grads(m)}
+            return [m], [x, cs, noise, t], [("step_with_noise, backward", call)]
+        return build
+
+    return [
+        ("1a EDM forward, plain", edm_forward(tiny, 0)),
+        ("1b EDM forward, cond_sample on a narrow stem (3 + 3)", edm_forward(narrow, 3)),
+        ("1c EDM forward, cond_sample on a wide stem (16 + 16)", edm_forward(wide, 16)),
+        ("2a EDM forward with grad and backward, narrow concat, eval mode", edm_forward_grad(narrow, 3, False)),
+        ("2b EDM forward with grad and backward, wide stem, train mode", edm_forward_grad(wide, 16, True)),
+        ("3a step_with_noise and loss.backward()", edm_step(tiny, 0, "step_with_noise")),
+        ("3b step_with_noise and loss.backward(), wide stem", edm_step(wide, 16, "step_with_noise")),
+        ("4a step_and_backward, one lane", edm_step(tiny, 0, "step_and_backward")),
+        ("4b step_and_backward, B = 16 on two lanes", edm_step(tiny, 0, "step_and_backward", B=16, lanes=2)),
+        ("4c edm_loss_and_grads, B = 16 on two lanes, narrow concat", edm_step(narrow, 3, "edm_loss_and_grads", B=16, lanes=2)),
+        ("5a sample_deterministically, one lane", edm_sample(tiny, 0, 2)),
+        ("5b sample_deterministically, one lane, wide stem", edm_sample(wide, 16, 2)),
+        ("5c sample_deterministically, B = 16 on two lanes", edm_sample(tiny, 0, 16, lanes=2)),
+        ("5d sample_deterministically, B = 16 on two lanes, narrow concat", edm_sample(narrow, 3, 16, lanes=2)),
+        ("5e sample_deterministically, use_graph='denoiser', capture and two replays", edm_sample(tiny, 0, 2, repeat=3, use_graph="denoiser")),
+        ("5f sample_deterministically, use_graph=True, capture and two replays", edm_sample(narrow, 3, 2, repeat=3, use_graph=True)),
+        ("6a sample_stochastically, given noises, one lane", edm_sample(narrow, 3, 2, churn=True, lanes=1)),
+        ("6b sample_stochastically, given noises, B = 16 on two lanes", edm_sample(tiny, 0, 16, churn=True, lanes=2)),
+        ("7a consistency forward, plain", cm(tiny, 0, "forward")),
+        ("7b consistency forward, narrow concat", cm(narrow, 3, "forward")),
+        ("7c consistency forward, wide stem", cm(wide, 16, "forward")),
+        ("7d consistency forward, B = 16, TQDNE_CM_LANES=2", cm(narrow, 3, "lanes", B=16)),
+        ("7e consistency sample_from, two sigmas", cm(tiny, 0, "sample_from")),
+        ("7f consistency step and backward, narrow concat", cm(narrow, 3, "step")),
+        ("8a DDPM step_with_noise and backward", ddpm(tiny, 0)),
+        ("8b DDPM step_with_noise and backward, cond_signal_input", ddpm(narrow, 3)),
+    ]
+
+
+def model_listing(out, outputs):
+    from tqdne_amd import _lib, engine, rng
+    rec = _lib._LIB = Recorder(_lib.load(), _lib._PROTOS)
+    for title, build in model_cases():
+        out.write(f"==== case {title}\n")
+        # (every case starts from an empty allocator: whether a temporary's address is later reused by something held, and so gets a
+        # name, then depends on the case alone, not on what earlier cases left cached)
+        mods = held = calls = names = None
+        gc.collect()
+        torch.cuda.empty_cache()
+        torch.manual_seed(0)
+        rng.seed_rank(0)
+        mods, held, calls = build()
+        names = Names()
+        for tag, call in calls:
+            rec.log = []
+            res = call()
+            torch.cuda.synchronize()
+            log, rec.log = rec.log, None
+            held.append(res)
+            names.seen.clear()
+            names.tmp = {}
+            for m in mods:   # (a module hands its parameters over; its scratch cache and its network's plans are looked up by name)
+                nets = [n for n in (getattr(m, "unet", None), getattr(m, "net", None)) if n is not None]
+                plans = [e for n in nets for e in n._engine_cache.values()]
+                for o in [m, *nets, getattr(m, "_scal", None), *plans, *(e._bwd for e in plans)]:
+                    names.gather(o)
+            names.gather(held)
+            names.gather(list(engine._PACK_TABLES.values()))
+            out.write(f"-- calls: {tag}\n")
+            streams = {}
+            for name, args in log:
+                s = stream_of(args)
+                out.write(f"     {names.call(name, args[:-1])} on stream {streams.setdefault(s, len(streams))}\n")
+            for k, v in res.items():
+                outputs[f"{'~' if k[0] == '~' else ''}{title} / {tag} / {k.lstrip('~')}"] = v.detach().clone().cpu()
+
+
 def movable_last(path):
     """the listing with the lines that may move (see --diff) put at the end of the run they belong to -- so a run that lost or gained one
     still differs -- and the buffers renumbered in that order of appearance within each case"""
@@ -271,11 +484,18 @@ if __name__ == "__main__":
         sys.exit(1 if d else 0)
     if sys.argv[1] == "--equal":
         a, b = torch.load(sys.argv[2]), torch.load(sys.argv[3])
-        bad = [k for k in a if k not in b or not torch.equal(a[k], b[k])] + [k for k in b if k not in a]
-        print(f"{len(a)} inference outputs, {len(bad)} differ", *bad, sep="\n  ")
+        exact = [k for k in set(a) | set(b) if k[0] != "~"]
+        bad = sorted(k for k in exact if k not in a or k not in b or not torch.equal(a[k], b[k]))
+        print(f"{len(exact)} inference outputs, {len(bad)} differ", *bad, sep="\n  ")
+        loose = sorted(k for k in a if k[0] == "~" and k in b)   # (through the gradient kernels' atomics: reported, not judged)
+        if loose:
+            diff = {k: float((a[k].double() - b[k].double()).abs().max()) for k in loose if not torch.equal(a[k], b[k])}
+            print(f"{len(loose)} losses / gradients, {len(diff)} not bit-equal, largest difference {max(diff.values(), default=0.0):.3e}")
         sys.exit(1 if bad else 0)
+    models = sys.argv[1] == "--models"
+    argv = sys.argv[2:] if models else sys.argv[1:]
     outs = {}
-    with open(sys.argv[1], "w") as f:
-        listing(f, outs)
-    if len(sys.argv) > 2:
-        torch.save(outs, sys.argv[2])
+    with open(argv[0], "w") as f:
+        (model_listing if models else listing)(f, outs)
+    if len(argv) > 1:
+        torch.save(outs, argv[1])

@@ -256,6 +256,11 @@ class TqError(RuntimeError):
     pass
 
 
+def _p(t):
+    """device address of a tensor for the C ABI (None stays None: an optional argument that is absent)"""
+    return None if t is None else t.data_ptr()
+
+
 def check(rc: int, what: str = ""):
     if rc != 0:
         kind = {-1: "TQ_ERR_ARG", -2: "TQ_ERR_SHAPE"}.get(rc, f"hipError_t {rc}")

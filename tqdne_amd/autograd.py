@@ -1,63 +1,70 @@
 """torch.autograd bridges: the HIP forward/backward of the EDM training step exposed as autograd Functions so
 that ``loss.backward()`` / Lightning / DDP see ordinary parameter gradients.  The arithmetic is entirely in
-libtqdne_hip.so; autograd only routes the resulting gradient tensors."""
+libtqdne_hip.so; autograd only routes the resulting gradient tensors.  ``check_fresh`` and ``loss_backward`` also serve the loss
+Functions of consistency_model.py and diffusion.py."""
 
 from __future__ import annotations
 
 import torch as th
 
 from . import _lib, engine, rng
-from ._lib import check
+from ._lib import _p, check
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
+def check_fresh(eng, fwd_id):
+    """A backward reads the activations its forward left in the plan's static buffers: refuse, before any launch, once a later
+    forward of the plan has overwritten them."""
+    if eng._fwd_count != fwd_id:
+        raise RuntimeError("another forward of the same shape ran between this forward and its backward: the execution plan's static "
+                           "buffers no longer hold its activations (call backward before the next forward of that shape)")
+
+
+def loss_backward(ctx, gloss, ninputs):
+    """Backward of a loss Function whose forward left ``eng``, ``fwd_id`` and ``dpred`` (d loss / d pred) in ``ctx``: parameter
+    gradients only, behind ``ninputs`` Nones for the Function's other inputs."""
+    check_fresh(ctx.eng, ctx.fwd_id)
+    return (None,) * ninputs + tuple(ctx.eng.backward(ctx.dpred, gloss))
+
+
+def edm_loss_forward(module, sample, eps, unit_noise, cond, cond_sample, lane=0):
+    """loss = mean(lambda(sigma) * (D(y + sigma*n; sigma) - y)^2)   (reference edm.py:126-134) on the plan and buffers of ``lane``.
+    Returns (loss, the plan that holds the activations, d loss / d pred)."""
+    lib = _lib.load()
+    B, _, T = sample.shape
+    per = sample[0].numel()
+    dev = sample.device
+    stream = th.cuda.current_stream(dev).cuda_stream
+    key = ("train", tuple(sample.shape), str(dev), lane)
+    bufs = module._scal.get(key)
+    if bufs is None:
+        bufs = dict(sigma=th.empty(B, device=dev), x=th.empty_like(sample), loss=th.empty(1, device=dev),
+                    dpred=th.empty_like(sample))
+        module._scal[key] = bufs
+    e = module.edm
+    check(lib.tq_edm_noise_inject(_p(sample), _p(unit_noise), _p(eps), float(e.P_mean), float(e.P_std), _p(bufs["sigma"]),
+                                  _p(bufs["x"]), B, per, stream), "noise inject")
+    pred = module._denoise_static(bufs["x"], bufs["sigma"], 1, cond, train=module.training, dropout_seed=rng.next_dropout_seed(),
+                                  cond_sample=cond_sample, lane=lane)
+    need_grad = any(p.requires_grad for p in module.unet.parameters())
+    check(lib.tq_edm_loss(_p(pred), _p(sample), _p(module._scalars(B, dev, lane)[4]), _p(bufs["loss"]),
+                          _p(bufs["dpred"]) if need_grad else None, B, per, stream), "edm loss")
+    # the plan that holds this forward's activations stays with the caller (the reference keeps its activations alive the same
+    # way): looked up again in backward it could be a NEW plan if the bounded cache evicted this one in between
+    return bufs["loss"][0].clone(), module.unet._engine(B, T, dev, lane), bufs["dpred"]
 
 
 class _EDMLossFn(th.autograd.Function):
-    """loss = mean(lambda(sigma) * (D(y + sigma*n; sigma) - y)^2)   (reference edm.py:126-134)."""
+    """``edm_loss_forward`` on lane 0 under autograd."""
 
     @staticmethod
     def forward(ctx, module, sample, eps, unit_noise, cond, cond_sample, *params):
-        lib = _lib.load()
-        B = sample.shape[0]
-        per = sample[0].numel()
-        dev = sample.device
-        stream = th.cuda.current_stream(dev).cuda_stream
-        key = ("train", tuple(sample.shape), str(dev), module._lane)
-        bufs = module._scal.get(key)
-        if bufs is None:
-            bufs = dict(sigma=th.empty(B, device=dev), x=th.empty_like(sample), loss=th.empty(1, device=dev),
-                        dpred=th.empty_like(sample))
-            module._scal[key] = bufs
-        e = module.edm
-        check(lib.tq_edm_noise_inject(_p(sample), _p(unit_noise), _p(eps), float(e.P_mean), float(e.P_std), _p(bufs["sigma"]),
-                                      _p(bufs["x"]), B, per, stream), "noise inject")
-        train = module.training
-        seed = rng.next_dropout_seed()
-        pred = module._denoise_static(bufs["x"], bufs["sigma"], 1, cond, train=train, dropout_seed=seed, cond_sample=cond_sample)
-        sc = module._scalars(B, dev)
-        need_grad = any(p.requires_grad for p in params)
-        check(lib.tq_edm_loss(_p(pred), _p(sample), _p(sc[4]), _p(bufs["loss"]), _p(bufs["dpred"]) if need_grad else None, B,
-                              per, stream), "edm loss")
-        ctx.module, ctx.bufs, ctx.shape, ctx.nparams = module, bufs, tuple(sample.shape), len(params)
-        ctx.cond = cond
-        ctx.concat = cond_sample is not None  # the stem then saw a pre-scaled, concatenated input
-        # the plan that holds this forward's activations stays with the graph (the reference keeps its activations alive the same
-        # way): looked up again in backward it could be a NEW plan if the bounded cache evicted this one in between
-        ctx.eng = module.unet._engine(B, sample.shape[2], dev, module._lane)
+        loss, ctx.eng, ctx.dpred = edm_loss_forward(module, sample, eps, unit_noise, cond, cond_sample)
         ctx.fwd_id = ctx.eng._fwd_count
-        ctx.scalars = module._scalars(B, dev)
-        return bufs["loss"][0].clone()
+        return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        eng, bufs, sc = ctx.eng, ctx.bufs, ctx.scalars
-        if eng._fwd_count != ctx.fwd_id:
-            raise RuntimeError("another forward of the same shape ran between this loss and its backward: the execution plan's static "
-                               "buffers no longer hold its activations (call backward before the next step of that shape)")
-        grads = eng.backward(bufs["dpred"], gloss, c_out=sc[1], in_scale=None if ctx.concat else sc[0])
-        return (None, None, None, None, None, None) + tuple(grads)
+        return loss_backward(ctx, gloss, 6)
 
 
 def edm_loss_and_grads(module, sample, eps, unit_noise, cond, cond_sample=None, lanes=None, on_bucket=None,
@@ -83,34 +90,22 @@ def edm_loss_and_grads(module, sample, eps, unit_noise, cond, cond_sample=None, 
     if lanes < 2 or B % lanes:
         lanes = 1
     dev = sample.device
-    h = B // lanes
-    main = th.cuda.current_stream(dev)
-    streams = [main] + [module._side_stream(dev, i) for i in range(1, lanes)]
-    cut = lambda t, i: None if t is None else t[i * h:(i + 1) * h].contiguous()
+    batch = (sample, eps, unit_noise, cond, cond_sample)
     losses, flats = [], []
     with th.no_grad():
-        for st in streams[1:]:
-            st.wait_stream(main)
-        try:
-            for i, st in enumerate(streams):
-                module._lane = i if lanes == 1 else engine.CONCURRENT_LANE0 + i
+        with engine.lane_fanout(dev, B, lanes) as fan:
+            for i, st in enumerate(fan.streams):
                 with th.cuda.stream(st):
-                    ctx = _Ctx()
-                    loss = _EDMLossFn.forward(ctx, module, cut(sample, i) if lanes > 1 else sample, cut(eps, i) if lanes > 1 else eps,
-                                              cut(unit_noise, i) if lanes > 1 else unit_noise, cut(cond, i) if lanes > 1 else cond,
-                                              cut(cond_sample, i) if lanes > 1 else cond_sample, *params)
-                    bufs, eng = ctx.bufs, ctx.eng
+                    # (one lane: the whole batch -- ``cut`` is then the tensor itself -- on the plan every other call of the shape uses)
+                    loss, eng, dpred = edm_loss_forward(module, *(fan.cut(t, i) for t in batch),
+                                                        lane=0 if lanes == 1 else engine.CONCURRENT_LANE0 + i)
                     scale = th.full((), 1.0 / lanes, device=dev)
-                    grads = eng.backward(bufs["dpred"], scale, clone=False, on_bucket=on_bucket if lanes == 1 else None,
+                    grads = eng.backward(dpred, scale, clone=False, on_bucket=on_bucket if lanes == 1 else None,
                                          bucket_elems=bucket_elems, tail_fill=tail_fill if lanes == 1 else None)
                     losses.append(loss)
                     flats.append(eng._bwd.flat)
                     if i == 0:
                         grads0, eng0_bwd = grads, eng._bwd
-        finally:
-            module._lane = 0
-        for i, st in enumerate(streams[1:], 1):
-            main.wait_stream(st)
         for f in flats[1:]:
             flats[0].add_(f)
         if on_bucket is not None and lanes > 1:
@@ -138,10 +133,6 @@ def train_lanes(B: int) -> int:
     return 1
 
 
-class _Ctx:
-    """stand-in for the autograd context when the loss Function's forward is driven directly"""
-
-
 def edm_loss(module, sample, eps, unit_noise, cond, cond_sample=None):
     params = [p for p in module.unet.parameters()]
     return _EDMLossFn.apply(module, sample, eps, unit_noise, cond, cond_sample, *params)
@@ -158,9 +149,8 @@ class _DenoiseFn(th.autograd.Function):
         train = module.training
         out = module._denoise_static(sample, sigma, 1, cond, train=train, dropout_seed=rng.next_dropout_seed() if train else 0,
                                      cond_sample=cond_sample)
-        ctx.module, ctx.shape, ctx.dev, ctx.lane = module, tuple(sample.shape), sample.device, module._lane
-        ctx.concat = cond_sample is not None
-        ctx.eng = module.unet._engine(sample.shape[0], sample.shape[2], sample.device, module._lane)
+        ctx.nch, ctx.concat = sample.shape[1], cond_sample is not None
+        ctx.eng = module.unet._engine(sample.shape[0], sample.shape[2], sample.device)
         ctx.fwd_id = ctx.eng._fwd_count
         ctx.want_dx = bool(sample.requires_grad)
         # (c_in / c_skip of THIS call: the module's scalar buffer is overwritten by the next call of the shape)
@@ -169,21 +159,18 @@ class _DenoiseFn(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        module, eng = ctx.module, ctx.eng
-        if eng._fwd_count != ctx.fwd_id:
-            raise RuntimeError("another forward of the same shape ran between this forward and its backward: the execution plan's "
-                               "static buffers no longer hold its activations (call backward before the next forward)")
-        B, _, T = ctx.shape
-        sc = module._scalars(B, ctx.dev)
-        one = th.ones((), device=ctx.dev)
+        eng = ctx.eng
+        check_fresh(eng, ctx.fwd_id)
+        one = th.ones((), device=gout.device)
         gout = gout.contiguous().float()
-        grads = eng.backward(gout, one, c_out=sc[1], in_scale=None if ctx.concat else sc[0], want_dx=ctx.want_dx)
+        # (c_out and, where the stem load applied it, c_in are those of the forward: the plan kept them with its activations)
+        grads = eng.backward(gout, one, want_dx=ctx.want_dx)
         dx = None
         if ctx.want_dx:
             c_in, c_skip = ctx.in_skip[0], ctx.in_skip[1]
             dx = eng._bwd.last_dx   # (already times c_in where the stem load applied it; the concatenated input was pre-scaled)
             if ctx.concat and not eng.wide_stem:   # (a wide stem's tq_btc_to_nct selected the sample's channels and applied c_in)
-                dx = dx[:, :ctx.shape[1]] * c_in[:, None, None]
+                dx = dx[:, :ctx.nch] * c_in[:, None, None]
             dx = dx + c_skip[:, None, None] * gout
         return (None, dx, None, None, None) + tuple(grads)
 
@@ -214,9 +201,7 @@ class _UNetFn(th.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         eng = ctx.eng
-        if eng._fwd_count != ctx.fwd_id:
-            raise RuntimeError("another forward of the same shape ran between this forward and its backward: the execution plan's "
-                               "static buffers no longer hold its activations (call backward before the next forward)")
+        check_fresh(eng, ctx.fwd_id)
         one = th.ones((), device=gy.device)
         grads = eng.backward(gy.contiguous().float(), one, want_dx=ctx.want_dx)
         return (None, eng._bwd.last_dx if ctx.want_dx else None, None, None) + tuple(grads)

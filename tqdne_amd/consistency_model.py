@@ -11,16 +11,11 @@ import numpy as np
 import torch
 
 from . import _lib, engine, rng
-from ._lib import check
+from ._lib import _p, check
 from ._cache import scratch_cache
-from .edm import sampler_lanes
+from .autograd import loss_backward
+from .edm import network_input, retry_on_range
 from .lightning_compat import LightningModule
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 
 
 class _ICTLossFn(torch.autograd.Function):
@@ -54,7 +49,6 @@ class _ICTLossFn(torch.autograd.Function):
         w = (1 / (sigmas[1:] - sigmas[:-1]))[timesteps].float().contiguous()   # (B,) weights: indexing glue, as the schedule
         check(lib.tq_pseudo_huber_loss(_p(pred), _p(bufs["target"]), _p(w), c, _p(bufs["loss"]), _p(bufs["dpred"]), B, per, stream),
               "pseudo-Huber loss")
-        ctx.module, ctx.shape = module, tuple(sample.shape)
         ctx.dpred = bufs["dpred"]
         # (the plan stays with the graph: a later look-up could find a NEW plan if the bounded cache evicted this one in between)
         ctx.eng = module.net._engine(B, sample.shape[2], dev)
@@ -63,12 +57,7 @@ class _ICTLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        eng = ctx.eng
-        if eng._fwd_count != ctx.fwd_id:
-            raise RuntimeError("another forward of the same shape ran between this loss and its backward: the execution plan's static "
-                               "buffers no longer hold its activations")
-        grads = eng.backward(ctx.dpred, gloss)
-        return (None,) * 7 + tuple(grads)
+        return loss_backward(ctx, gloss, 7)
 
 
 class LithningConsistencyModel(LightningModule):  # (sic) the reference's class name
@@ -98,19 +87,9 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         check(lib.tq_cm_scalars(_p(sigma), 1, float(self.sigma_data), float(self.sigma_min), _p(sc[0]), _p(sc[1]), B, stream),
               "cm scalars")
         eng = self.net._engine(B, T, dev, lane)
-        x_in = sample
-        if cond_sample is not None and eng.wide_stem:   # (the stem's layout kernel concatenates the conditioning signal itself)
-            return eng.forward(sample, sigma, cond, in_scale=None, c_out=sc[0], c_skip=sc[1], skip_src=sample, train=train,
-                               dropout_seed=dropout_seed, infer=infer, cond_x=cond_sample)
-        if cond_sample is not None:
-            C1 = cond_sample.shape[1]
-            kx = ("x_in", B, sample.shape[1] + C1, T, str(dev), lane)
-            x_in = self._scal.get(kx)
-            if x_in is None:
-                x_in = self._scal[kx] = torch.empty(B, sample.shape[1] + C1, T, device=dev)
-            check(lib.tq_concat_scale(_p(sample), None, _p(cond_sample), _p(x_in), B, sample.shape[1], C1, T, stream), "concat")
+        x_in, _, cond_x = network_input(eng, self._scal, lane, sample, None, cond_sample)
         return eng.forward(x_in, sigma, cond, in_scale=None, c_out=sc[0], c_skip=sc[1], skip_src=sample, train=train,
-                           dropout_seed=dropout_seed, infer=infer)
+                           dropout_seed=dropout_seed, infer=infer, cond_x=cond_x)
 
     def forward(self, sample, sigma, cond_sample=None, cond=None, _check_range=True):
         """consistency_model.py:63-79."""
@@ -126,31 +105,17 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
             lanes = 1
         if lanes < 2:
             infer = not torch.is_grad_enabled()
-            y = self._forward_static(sample, sigma, cond, infer=infer, cond_sample=cond_sample).clone()
-            if infer and _check_range and self.net._engine(B, sample.shape[2], sample.device, 0).check_range():
-                y = self._forward_static(sample, sigma, cond, infer=infer, cond_sample=cond_sample).clone()  # (the plan is on bf16x3 now)
-            return y
+            eng = self.net._engine(B, sample.shape[2], sample.device) if infer and _check_range else None   # (None: no flag read)
+            return retry_on_range(eng, lambda: self._forward_static(sample, sigma, cond, infer=infer, cond_sample=cond_sample).clone())
         # independent samples: sub-batches on separate HIP streams run out of phase (see LightningEDM.sample_deterministically)
-        dev = sample.device
-        h = B // lanes
-        main = torch.cuda.current_stream(dev)
         out = torch.empty_like(sample[:, : self.net.out_channels])
-        for i in range(lanes):
-            st = main if i == 0 else self._side_stream(dev, i)
-            if i:
-                st.wait_stream(main)
-            with torch.cuda.stream(st):
-                sl = slice(i * h, (i + 1) * h)
-                y = self._forward_static(sample[sl].contiguous(), sigma[sl].contiguous(),
-                                         None if cond is None else cond[sl].contiguous(), lane=engine.CONCURRENT_LANE0 + i, infer=True,
-                                         cond_sample=None if cond_sample is None else cond_sample[sl].contiguous())
-                out[sl].copy_(y)
-        for i in range(1, lanes):
-            main.wait_stream(self._side_stream(dev, i))
+        with engine.lane_fanout(sample.device, B, lanes) as fan:
+            for i, st in enumerate(fan.streams):
+                with torch.cuda.stream(st):
+                    y = self._forward_static(fan.cut(sample, i), fan.cut(sigma, i), fan.cut(cond, i), lane=engine.CONCURRENT_LANE0 + i,
+                                             infer=True, cond_sample=fan.cut(cond_sample, i))
+                    out[fan.rows(i)].copy_(y)
         return out
-
-    def _side_stream(self, dev, i):
-        return engine.side_stream(dev, i)   # (one pool per process, see engine.side_stream)
 
     @torch.no_grad()
     def sample(self, shape, sigmas=[1.0], cond_sample=None, cond=None):
@@ -167,13 +132,8 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
                 sample = sample + u * sigma
                 sample = self(sample, ones * sigma, cond_sample, cond, _check_range=False)
             return sample
-        out = run()
-        # range guard of the fp16-range conv scheme: ONE flag read per sample call (as the EDM samplers do), not one per network
-        # evaluation; if a tensor came near the fp16 range the plans are on bf16x3 now and the sampling is repeated
-        eng = self.net._engine(epsilon.shape[0], epsilon.shape[2], epsilon.device, 0)
-        if eng.check_range():
-            out = run()
-        return out
+        # range guard: ONE flag read per sample call (as the EDM samplers do), not one per network evaluation
+        return retry_on_range(lambda: self.net._engine(epsilon.shape[0], epsilon.shape[2], epsilon.device), run)
 
     # ------------------------------------------------------------------ iCT training (consistency_model.py:115-190)
     def _schedule(self):
@@ -195,8 +155,9 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         dropout masks as the student), student at sigma_{t+1}, weighted pseudo-Huber distance.  Both UNet passes and the
         backward are HIP; the schedule, the (B,)-sized draws and the loss on the (B, C, T) outputs are torch glue."""
         sample = batch["signal"]
-        cond_sample = batch["cond_signal"].detach().contiguous().float() if "cond_signal" in batch else None
-        cond = batch["cond"] if "cond" in batch else None
+        cond_sample, cond = batch.get("cond_signal"), batch.get("cond")
+        if cond_sample is not None:
+            cond_sample = cond_sample.detach().contiguous().float()
         sigmas = self._schedule()
         z = lambda s_: torch.erf((torch.log(s_) - self.lognormal_mean) / (self.lognormal_std * np.sqrt(2)))
         pdf = z(sigmas[1:]) - z(sigmas[:-1])
@@ -220,6 +181,4 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
 
     def evaluate(self, batch, sigmas=[1]):
         sample = batch["signal"]
-        cond_sample = batch["cond_signal"] if "cond_signal" in batch else None
-        cond = batch["cond"] if "cond" in batch else None
-        return self.sample(sample.shape, sigmas, cond_sample, cond)
+        return self.sample(sample.shape, sigmas, batch.get("cond_signal"), batch.get("cond"))

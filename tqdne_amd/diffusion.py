@@ -21,12 +21,9 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib, engine, rng
-from ._lib import check
+from ._lib import _p, check
+from .autograd import loss_backward
 from .lightning_compat import LightningModule
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 class DDPMScheduler:
@@ -161,16 +158,12 @@ class _DDPMLossFn(torch.autograd.Function):
         loss = torch.empty(1, device=dev)
         dpred = torch.empty_like(pred)
         check(lib.tq_mse_loss(_p(pred), _p(target), _p(loss), _p(dpred), pred.numel(), stream), "mse loss")
-        ctx.eng, ctx.dpred, ctx.fwd_id, ctx.train = eng, dpred, eng._fwd_count, train
+        ctx.eng, ctx.dpred, ctx.fwd_id = eng, dpred, eng._fwd_count
         return loss[0].clone()
 
     @staticmethod
     def backward(ctx, gloss):
-        eng = ctx.eng
-        if eng._fwd_count != ctx.fwd_id:
-            raise RuntimeError("another forward of the same shape ran between this forward and its backward")
-        grads = eng.backward(ctx.dpred, gloss)
-        return (None,) * 6 + tuple(grads)
+        return loss_backward(ctx, gloss, 6)
 
 
 class LightningDDMP(LightningModule):

@@ -22,7 +22,7 @@ import torch as th
 
 from . import _lib, engine
 from ._cache import scratch_cache
-from ._lib import check
+from ._lib import _p, check
 from .lightning_compat import LightningModule
 from .unet import UNetModel
 
@@ -89,8 +89,110 @@ def sampler_lanes(B: int) -> int:
     return 1
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
+def network_input(eng, cache, lane, sample, scale, cond_sample):
+    """What ``eng.forward`` takes as (x, in_scale, cond_x) for a network input of ``scale * sample`` (``scale``: (B,) or None) with the
+    conditioning signal ``cond_sample``, if any, concatenated unscaled on the channel axis behind it (edm.py:108-109,
+    consistency_model.py:63-66).  No signal: the scale rides in the stem load.  A wide stem (more than 16 input channels): its layout
+    kernel scales the sample and concatenates the signal itself.  A narrow one: the scale cannot ride in the stem load (only the first
+    channels are scaled), so one fused concat + scale launch into a buffer kept in ``cache`` per shape and ``lane``."""
+    if cond_sample is None:
+        return sample, scale, None
+    cond_sample = cond_sample.contiguous().float()
+    if eng.wide_stem:
+        return sample, scale, cond_sample
+    (B, C0, T), C1, dev = sample.shape, cond_sample.shape[1], sample.device
+    key = ("cat", B, C0, C1, T, str(dev), lane)
+    x_in = cache.get(key)
+    if x_in is None:
+        x_in = cache[key] = th.empty(B, C0 + C1, T, dtype=th.float32, device=dev)
+    check(_lib.load().tq_concat_scale(_p(sample), _p(scale), _p(cond_sample), _p(x_in), B, C0, C1, T,
+                                      th.cuda.current_stream(dev).cuda_stream), "concat + scale")
+    return x_in, None, None
+
+
+def retry_on_range(eng, run):
+    """Range guard of the fp16-range conv scheme around ``run()``: ONE flag read (a synchronisation) once its launches are enqueued; if a
+    tensor came near the fp16 range the model's plans have been moved to bf16x3 and ``run()`` is repeated.  ``eng``: the plan that is
+    asked -- or a callable that finds it afterwards, for a run that builds the plans it uses (None then: nothing to ask)."""
+    out = run()
+    if callable(eng):
+        eng = eng()
+    if eng is not None and eng.check_range():
+        out = run()
+    return out
+
+
+def replay_graph(eng, graph, refresh):
+    """Replay a HIP graph captured from ``eng``'s launches on the current stream.  The captured launches read the model's packed weight
+    fragments at fixed addresses: they are brought up to date with the parameters (an optimizer step since the last call) BEFORE the
+    replay -- inside a forward this is the first thing eng.forward does.  ``refresh(stream)`` then copies this call's inputs into the
+    static buffers the graph reads."""
+    stream = th.cuda.current_stream(eng.dev).cuda_stream
+    eng.repack(stream)
+    refresh(stream)
+    graph.replay()
+    eng._mark_use(stream)   # (a repack issued on another stream must wait for this replay's reads of the fragments)
+
+
+class _HeunRun:
+    """The Heun integration (edm.py:171-230) of one batch -- or one lane's sub-batch -- as a resumable object, bound at creation to its
+    ``lane``: the execution plan, scalars and fp64 sampler buffers of that lane.  ``advance()`` enqueues one sampler step on the
+    current stream; ``x`` is the fp64 state, the result once ``done``.
+    ``churn`` = (sigma_hat (steps,), coefficients (steps,), noise_of_step): the stochastic sampler's steps (edm.py:198-230) -- the
+    noise increase ``tq_heun_churn`` with ``noise_of_step(i)``, this batch's unit noise of step i, then the Heun step from the
+    increased state ``xh`` at sigma_hat instead of from ``x`` at sigma."""
+
+    def __init__(self, edm, start, sigmas, cond_sample, cond, lane=0, use_graph=False, churn=None):
+        self.edm, self.lane, self.churn = edm, lane, churn
+        self.sigmas = sigmas.to(device=start.device, dtype=th.float32).contiguous()
+        self.cond = None if cond is None else cond.contiguous().float()
+        self.cond_sample = None if cond_sample is None else cond_sample.contiguous().float()
+        bufs = edm._sampler_buffers(start, lane)
+        self.x, self.xn, self.d, self.x32 = bufs["x"], bufs["xn"], bufs["d"], bufs["x32"]
+        self.x.copy_(start)
+        if churn is None:
+            self.x32.copy_(start)  # fp64 -> fp32 rounding, as sample_curr.to(self.dtype)
+        else:   # (tq_heun_churn writes x32 before the first network evaluation reads it)
+            if "xh" not in bufs:
+                bufs["xh"] = th.empty_like(self.x)
+            self.xh = bufs["xh"]
+        self.i, self.nsteps = 0, self.sigmas.numel() - 1
+        self.replay = edm._graph_denoiser(bufs, self.x32, self.cond, self.cond_sample, lane) if use_graph else None
+
+    @property
+    def done(self):
+        return self.i >= self.nsteps
+
+    def denoise(self, sig_ptr):
+        if self.replay is not None:
+            return self.replay(sig_ptr)
+        return self.edm._denoise_static(self.x32, _RawPtr(sig_ptr), 0, self.cond, cond_sample=self.cond_sample, infer=True,
+                                        lane=self.lane)
+
+    def advance(self):
+        lib, edm, i, n = _lib.load(), self.edm, self.i, self.x.numel()
+        stream = th.cuda.current_stream(self.x.device).cuda_stream
+        src, s_from, s_next = self.x, self.sigmas.data_ptr() + 4 * i, self.sigmas.data_ptr() + 4 * (i + 1)
+        if self.churn is not None:
+            shat, coef, noise_of_step = self.churn
+            unit = noise_of_step(i)   # (a lane's slice is registered with its stream: safe to let go once the launch is enqueued)
+            src, s_from = self.xh, shat.data_ptr() + 4 * i
+            check(lib.tq_heun_churn(_p(self.x), _p(unit), coef.data_ptr() + 4 * i, float(edm.edm.S_noise), _p(src), _p(self.x32), n,
+                                    stream), "heun churn")
+        den = self.denoise(s_from)
+        check(lib.tq_heun_euler(_p(src), _p(den), s_from, s_next, _p(self.d), _p(self.xn), _p(self.x32), n, stream), "heun euler")
+        if i < edm.num_sampling_steps - 1:
+            den = self.denoise(s_next)
+            check(lib.tq_heun_correct(_p(src), _p(self.xn), _p(den), _p(self.d), s_from, s_next, _p(self.x), _p(self.x32), n, stream),
+                  "heun correct")
+        else:
+            self.x, self.xn = self.xn, self.x
+        self.i += 1
+
+    def finish(self):
+        while not self.done:
+            self.advance()
+        return self.x
 
 
 class LightningEDM(LightningModule):
@@ -116,49 +218,30 @@ class LightningEDM(LightningModule):
                 param.requires_grad = False
         self.save_hyperparameters(ignore=("autoencoder"))
         self._scal = scratch_cache()
-        self._lane = 0  # which set of static buffers / execution plan the calls below use (two-lane sampling)
 
     # ------------------------------------------------------------------ preconditioned network
-    def _scalars(self, B, device):
-        key = (B, str(device), self._lane)
+    # (``lane``: which set of static buffers / execution plan a call uses -- 0, or a lane of a multi-stream sampler / training step)
+    def _scalars(self, B, device, lane=0):
+        key = (B, str(device), lane)
         s = self._scal.get(key)
         if s is None:
             s = th.empty(5, B, dtype=th.float32, device=device)  # c_in, c_out, c_skip, c_noise, loss weight
             self._scal[key] = s
         return s
 
-    def _denoise_static(self, sample, sigma, sigma_stride, cond, train=False, dropout_seed=0, cond_sample=None, infer=False):
+    def _denoise_static(self, sample, sigma, sigma_stride, cond, train=False, dropout_seed=0, cond_sample=None, infer=False, lane=0):
         """Fused preconditioned forward (edm.py:105-113); returns the engine's static output buffer.
         ``sigma``: device tensor; ``sigma_stride`` 1 (per-sample) or 0 (one value shared by the batch).
-        ``cond_sample``: conditioning signal concatenated on the channel axis behind the scaled sample (edm.py:108-109); the
-        pre-scale then cannot ride in the stem load (only the first channels are scaled): one fused concat + scale launch."""
-        lib = _lib.load()
+        ``cond_sample``: conditioning signal concatenated on the channel axis behind the scaled sample (see network_input)."""
         B, _, T = sample.shape
         dev = sample.device
-        sc = self._scalars(B, dev)
-        stream = th.cuda.current_stream(dev).cuda_stream
-        check(lib.tq_edm_scalars(_p(sigma), sigma_stride, float(self.edm.sigma_data), _p(sc[0]), _p(sc[1]), _p(sc[2]),
-                                 _p(sc[3]), _p(sc[4]), B, stream), "edm scalars")
-        if cond_sample is not None and self.unet._engine(B, T, dev, self._lane).wide_stem:
-            # more than 16 input channels: the stem's layout kernel scales the sample and concatenates the conditioning signal itself
-            eng = self.unet._engine(B, T, dev, self._lane)
-            return eng.forward(sample, sc[3], cond, in_scale=sc[0], c_out=sc[1], c_skip=sc[2], skip_src=sample, train=train,
-                               dropout_seed=dropout_seed, infer=infer, cond_x=cond_sample.contiguous().float())
-        if cond_sample is not None:
-            C1 = cond_sample.shape[1]
-            key = ("cat", B, sample.shape[1], C1, T, str(dev), self._lane)
-            x_in = self._scal.get(key)
-            if x_in is None:
-                x_in = th.empty(B, sample.shape[1] + C1, T, dtype=th.float32, device=dev)
-                self._scal[key] = x_in
-            check(lib.tq_concat_scale(_p(sample), _p(sc[0]), _p(cond_sample.contiguous().float()), _p(x_in), B, sample.shape[1], C1, T,
-                                      stream), "concat + scale")
-            eng = self.unet._engine(B, T, dev, self._lane)
-            return eng.forward(x_in, sc[3], cond, in_scale=None, c_out=sc[1], c_skip=sc[2], skip_src=sample, train=train,
-                               dropout_seed=dropout_seed, infer=infer)
-        eng = self.unet._engine(B, T, dev, self._lane)
-        return eng.forward(sample, sc[3], cond, in_scale=sc[0], c_out=sc[1], c_skip=sc[2], skip_src=sample, train=train,
-                           dropout_seed=dropout_seed, infer=infer)
+        sc = self._scalars(B, dev, lane)
+        check(_lib.load().tq_edm_scalars(_p(sigma), sigma_stride, float(self.edm.sigma_data), _p(sc[0]), _p(sc[1]), _p(sc[2]),
+                                         _p(sc[3]), _p(sc[4]), B, th.cuda.current_stream(dev).cuda_stream), "edm scalars")
+        eng = self.unet._engine(B, T, dev, lane)
+        x_in, in_scale, cond_x = network_input(eng, self._scal, lane, sample, sc[0], cond_sample)
+        return eng.forward(x_in, sc[3], cond, in_scale=in_scale, c_out=sc[1], c_skip=sc[2], skip_src=sample, train=train,
+                           dropout_seed=dropout_seed, infer=infer, cond_x=cond_x)
 
     def forward(self, sample, sigma, cond_sample=None, cond=None):
         """Make a forward pass through the network with skip connection (edm.py:105-113)."""
@@ -178,17 +261,14 @@ class LightningEDM(LightningModule):
             # (dropout only in training mode)
             from .autograd import denoise_with_grad
             return denoise_with_grad(self, sample, sigma, cond, cond_sample)
-        y = self._denoise_static(sample, sigma, 1, cond, cond_sample=cond_sample, infer=True).clone()
-        if self.unet._engine(sample.shape[0], sample.shape[2], sample.device, self._lane).check_range():
-            y = self._denoise_static(sample, sigma, 1, cond, cond_sample=cond_sample, infer=True).clone()  # (now on bf16x3)
-        return y
+        return retry_on_range(self.unet._engine(sample.shape[0], sample.shape[2], sample.device),
+                              lambda: self._denoise_static(sample, sigma, 1, cond, cond_sample=cond_sample, infer=True).clone())
 
     # ------------------------------------------------------------------ training
     def step(self, batch, batch_idx):
         """A single step in the training loop (edm.py:115-134)."""
         sample = batch["signal"]
-        cond_sample = batch["cond_signal"] if "cond_signal" in batch else None
-        cond = batch["cond"] if "cond" in batch else None
+        cond_sample, cond = batch.get("cond_signal"), batch.get("cond")
         if self.autoencoder:
             sample = self.autoencoder.encode(sample)
             if cond_sample is not None:
@@ -214,8 +294,7 @@ class LightningEDM(LightningModule):
         if self.unet.dims == 2:
             raise NotImplementedError("DataParallelTrainer drives the 1-D HIP path; train dims=2 models with step() + torch.autograd")
         sample = batch["signal"]
-        cond = batch["cond"] if "cond" in batch else None
-        cond_sample = batch["cond_signal"] if "cond_signal" in batch else None
+        cond_sample, cond = batch.get("cond_signal"), batch.get("cond")
         if self.autoencoder:
             with th.no_grad():
                 sample = self.autoencoder.encode(sample)
@@ -266,8 +345,8 @@ class LightningEDM(LightningModule):
             return self.autoencoder.decode(sample)
         return sample
 
-    def _sampler_buffers(self, eps):
-        key = ("smp", tuple(eps.shape), str(eps.device), self._lane)
+    def _sampler_buffers(self, eps, lane=0):
+        key = ("smp", tuple(eps.shape), str(eps.device), lane)
         bufs = self._scal.get(key)
         if bufs is None:
             f64 = lambda: th.empty(eps.shape, dtype=th.float64, device=eps.device)
@@ -297,14 +376,11 @@ class LightningEDM(LightningModule):
             raise RuntimeError("tqdne_amd samples on MI355X HIP kernels only; got a CPU start state")
         if use_graph is None:
             use_graph = os.environ.get("TQDNE_SAMPLER_GRAPH") == "1" and lanes is None and not th.cuda.is_current_stream_capturing()
-        out = self._sample_det(eps, sigmas, cond_sample, cond, use_graph, lanes)
-        # range guard of the fp16-range conv scheme: one flag read per sample call; if a tensor came near the fp16 range the plans
-        # have been moved to bf16x3 and the integration is repeated
-        # (the flag is one per model and device, shared by every lane's plan: one read)
-        engs = [e for e in self.unet._engine_cache.values() if e.dev == eps.device]
-        if engs and engs[0].check_range():
-            out = self._sample_det(eps, sigmas, cond_sample, cond, use_graph, lanes)
-        return out
+        # range guard: one flag read per sample call (the flag is one per model and device, shared by every lane's plan)
+        return retry_on_range(lambda: self._any_plan(eps.device), lambda: self._sample_det(eps, sigmas, cond_sample, cond, use_graph, lanes))
+
+    def _any_plan(self, dev):
+        return next((e for e in self.unet._engine_cache.values() if e.dev == dev), None)
 
     def _sample_det(self, eps, sigmas, cond_sample, cond, use_graph, lanes):
         B = eps.shape[0]
@@ -316,52 +392,32 @@ class LightningEDM(LightningModule):
             return self._graph_sample(eps, sigmas, cond_sample, cond)
         use_graph = bool(use_graph)   # ("denoiser": the per-evaluation graph below)
         if lanes < 2 or B % lanes or B // lanes < 8:
-            run = self._heun_lane(eps, sigmas, cond_sample, cond, use_graph)
-            for _ in run:
-                pass
-            res = run.result.clone()
-            run.release()
-            return res
+            return _HeunRun(self, eps, sigmas, cond_sample, cond, 0, use_graph).finish().clone()
         return self._run_lanes(eps, sigmas, cond_sample, cond, lanes, use_graph)
 
     def _run_lanes(self, eps, sigmas, cond_sample, cond, lanes, use_graph=False, churn=None):
         """``lanes`` sub-batches integrated concurrently on as many HIP streams (see sample_deterministically); ``churn``: the
         stochastic sampler's (sigma_hat, coefficients, unit noises per step for the WHOLE batch) -- every lane takes its slice."""
-        B = eps.shape[0]
-        dev = eps.device
-        h = B // lanes
-        cut = lambda t, i: None if t is None else t[i * h:(i + 1) * h].contiguous()
-        main = th.cuda.current_stream(dev)
-        streams = [main] + [self._side_stream(dev, i) for i in range(1, lanes)]
-        for st in streams[1:]:
-            st.wait_stream(main)
-        runs = []
-        try:
-            for i, st in enumerate(streams):
-                self._lane = engine.CONCURRENT_LANE0 + i
+        with engine.lane_fanout(eps.device, eps.shape[0], lanes) as fan:
+            runs = []
+            for i, st in enumerate(fan.streams):
                 with th.cuda.stream(st):
                     lane_churn = None
                     if churn is not None:
                         shat, coef, noises = churn
-                        lane_churn = (shat, coef, lambda k, _i=i, _st=st: noises.take(k, _i, h, _st))
-                    runs.append(self._heun_lane(cut(eps, i), sigmas, cut(cond_sample, i), cut(cond, i), use_graph, churn=lane_churn))
+                        lane_churn = (shat, coef, lambda k, _i=i, _st=st: noises.take(k, _i, fan.h, _st))
+                    runs.append(_HeunRun(self, fan.cut(eps, i), sigmas, fan.cut(cond_sample, i), fan.cut(cond, i),
+                                         engine.CONCURRENT_LANE0 + i, use_graph, lane_churn))
             # one sampler step of lane 0, then of lane 1, ...: all queues stay fed well ahead of the GPU
             while not all(r.done for r in runs):
-                for i, (r, st) in enumerate(zip(runs, streams)):
+                for r, st in zip(runs, fan.streams):
                     if not r.done:
-                        self._lane = engine.CONCURRENT_LANE0 + i
                         with th.cuda.stream(st):
                             r.advance()
-        finally:
-            self._lane = 0
-        out = th.empty_like(eps)
-        for i, st in enumerate(streams[1:], 1):
-            with th.cuda.stream(st):
-                out[i * h:(i + 1) * h].copy_(runs[i].result)
-            main.wait_stream(st)
-        out[:h].copy_(runs[0].result)
-        for r in runs:
-            r.release()
+            out = th.empty_like(eps)
+            for i, st in enumerate(fan.streams):
+                with th.cuda.stream(st):
+                    out[fan.rows(i)].copy_(runs[i].x)
         return out
 
     class _StepNoises:
@@ -398,103 +454,14 @@ class LightningEDM(LightningModule):
                 del self.live[k]
             return t[lane * h:(lane + 1) * h]
 
-    def _side_stream(self, dev, i=1):
-        return engine.side_stream(dev, i)   # (one pool per process: the number of live streams matters, see engine.side_stream)
-
-    def _heun_lane(self, eps, sigmas, cond_sample, cond, use_graph, churn=None):
-        """The Heun integration of one (half) batch as a resumable object: ``advance()`` enqueues one sampler step on the current
-        stream with the current lane's plan and buffers; ``result`` is the fp64 state buffer once ``done``.
-        ``churn`` = (sigma_hat (steps,), coefficients (steps,), noise_of_step): the stochastic sampler's steps (edm.py:198-230) -- the
-        noise increase ``tq_heun_churn`` with this lane's slice ``noise_of_step(i)`` of the step's unit noise, then the Heun step from
-        sigma_hat instead of sigma."""
-        lib = _lib.load()
-        dev = eps.device
-        sigmas = sigmas.to(device=dev, dtype=th.float32).contiguous()
-        if cond is not None:
-            cond = cond.contiguous().float()
-        if cond_sample is not None:
-            cond_sample = cond_sample.contiguous().float()
-        bufs = self._sampler_buffers(eps)
-        edm = self
-
-        class _Run:
-            def __init__(r, start):
-                # (``start`` is an argument, not a closure variable: a class object sits in reference cycles of its own, and a
-                # cell holding a view of the caller's start state would keep that whole allocation alive until a cyclic GC pass)
-                r.x, r.xn, r.d, r.x32 = bufs["x"], bufs["xn"], bufs["d"], bufs["x32"]
-                if churn is not None:
-                    if "xh" not in bufs:
-                        bufs["xh"] = th.empty_like(bufs["x"])
-                    r.xh = bufs["xh"]
-                r.x.copy_(start)
-                r.x32.copy_(start)  # fp64 -> fp32 rounding, as sample_curr.to(self.dtype)
-                r.i, r.nsteps = 0, sigmas.numel() - 1
-                r.keep = (sigmas, cond, cond_sample)
-                if use_graph:
-                    r.denoise = edm._graph_denoiser(bufs, r.x32, cond, cond_sample)
-                else:
-                    r.denoise = lambda sig_ptr: edm._denoise_static(r.x32, _RawPtr(sig_ptr), 0, cond, cond_sample=cond_sample, infer=True)
-
-            @property
-            def done(r):
-                return r.i >= r.nsteps
-
-            @property
-            def result(r):
-                return r.x
-
-            def advance(r):
-                i, n, sp = r.i, r.x.numel(), sigmas.data_ptr()
-                stream = th.cuda.current_stream(dev).cuda_stream
-                s_i, s_n = sp + 4 * i, sp + 4 * (i + 1)
-                if churn is not None:
-                    shat, coef, noise_of_step = churn
-                    unit = noise_of_step(i)   # (a slice registered with this lane's stream: safe to let go once the launch is enqueued)
-                    s_hat = shat.data_ptr() + 4 * i
-                    check(lib.tq_heun_churn(_p(r.x), _p(unit), coef.data_ptr() + 4 * i, float(edm.edm.S_noise), _p(r.xh), _p(r.x32), n,
-                                            stream), "heun churn")
-                    den = r.denoise(s_hat)
-                    check(lib.tq_heun_euler(_p(r.xh), _p(den), s_hat, s_n, _p(r.d), _p(r.xn), _p(r.x32), n, stream), "heun euler")
-                    if i < edm.num_sampling_steps - 1:
-                        den = r.denoise(s_n)
-                        check(lib.tq_heun_correct(_p(r.xh), _p(r.xn), _p(den), _p(r.d), s_hat, s_n, _p(r.x), _p(r.x32), n, stream),
-                              "heun correct")
-                    else:
-                        r.x, r.xn = r.xn, r.x
-                    r.i += 1
-                    return
-                den = r.denoise(s_i)
-                check(lib.tq_heun_euler(_p(r.x), _p(den), s_i, s_n, _p(r.d), _p(r.xn), _p(r.x32), n, stream), "heun euler")
-                if i < edm.num_sampling_steps - 1:
-                    den = r.denoise(s_n)
-                    check(lib.tq_heun_correct(_p(r.x), _p(r.xn), _p(den), _p(r.d), s_i, s_n, _p(r.x), _p(r.x32), n, stream),
-                          "heun correct")
-                else:
-                    r.x, r.xn = r.xn, r.x
-                r.i += 1
-
-            def __iter__(r):
-                while not r.done:
-                    r.advance()
-                    yield r.i
-
-            def release(r):
-                """drop the references that tie this object into a cycle (closure <-> instance): the start state and the
-                conditioning tensors would otherwise stay allocated until Python's cyclic collector gets round to it"""
-                r.keep = r.denoise = None
-
-        run = _Run(eps)
-        del eps
-        return run
-
-    def _graph_sample(self, eps, sigmas, cond_sample, cond):
+    def _graph_sample(self, eps, sigmas, cond_sample, cond, lane=0):
         """The whole Heun integration as ONE HIP graph.  Everything the captured launches read lives in static buffers of the sampler
         (start state, sigma schedule, conditioning), refreshed by device-to-device copies before each replay; the graph is re-captured
         when the shapes, the number of steps or the plan (weights format, see the range guard) change."""
         dev = eps.device
         B = eps.shape[0]
-        bufs = self._sampler_buffers(eps)
-        eng = self.unet._engine(B, eps.shape[2], dev, self._lane)
+        bufs = self._sampler_buffers(eps, lane)
+        eng = self.unet._engine(B, eps.shape[2], dev, lane)
         nsig = int(sigmas.numel())
         key = (nsig, None if cond is None else tuple(cond.shape), None if cond_sample is None else tuple(cond_sample.shape),
                eng.uid, eng.plan_epoch, self.num_sampling_steps)
@@ -502,75 +469,55 @@ class LightningEDM(LightningModule):
         live = {e.uid for e in self.unet._engine_cache.values()}
         for k_ in [k_ for k_ in cache if k_[3] not in live]:   # graphs of evicted plans: their launches point into freed buffers
             del cache[k_]
+
+        def refresh(st):
+            for name, t in (("sig", sigmas), ("start", eps), ("cond", cond), ("cs", cond_sample)):
+                if t is not None:
+                    st[name].copy_(t)
+
         g = cache.get(key)
         if g is None:
             st = dict(key=key, sig=th.empty(nsig, dtype=th.float32, device=dev), start=th.empty_like(bufs["x"]),
                       cond=None if cond is None else th.empty(cond.shape, dtype=th.float32, device=dev),
                       cs=None if cond_sample is None else th.empty(cond_sample.shape, dtype=th.float32, device=dev))
-            st["sig"].copy_(sigmas)
-            st["start"].copy_(eps)
-            if cond is not None:
-                st["cond"].copy_(cond)
-            if cond_sample is not None:
-                st["cs"].copy_(cond_sample)
+            refresh(st)
             # warm-up outside capture: plan build, weight packing, allocator state
-            run = self._heun_lane(st["start"], st["sig"], st["cs"], st["cond"], False)
-            run.advance()
-            run.release()
+            _HeunRun(self, st["start"], st["sig"], st["cs"], st["cond"], lane).advance()
             th.cuda.synchronize(dev)
             graph = th.cuda.CUDAGraph()
             # thread-local capture: other threads of the process (a DataLoader's pin-memory thread, RCCL's watchdog) may allocate
             # or record events meanwhile without invalidating it
             with th.cuda.graph(graph, capture_error_mode="thread_local"):
-                run = self._heun_lane(st["start"], st["sig"], st["cs"], st["cond"], False)
-                for _ in run:
-                    pass
-                st["out"] = run.result
-                run.release()
+                st["out"] = _HeunRun(self, st["start"], st["sig"], st["cs"], st["cond"], lane).finish()
             st["graph"] = graph
             while len(cache) >= 4:   # (each graph owns a private pool: keep a handful, drop the oldest)
                 cache.pop(next(iter(cache)))
             cache[key] = g = st
-        # the captured launches read the model's packed weight fragments at fixed addresses: bring them up to date with the parameters
-        # (an optimizer step since the last call) BEFORE the replay -- inside a forward this is the first thing eng.forward does
-        stream = th.cuda.current_stream(dev).cuda_stream
-        eng.repack(stream)
-        g["sig"].copy_(sigmas)
-        g["start"].copy_(eps)
-        if cond is not None:
-            g["cond"].copy_(cond)
-        if cond_sample is not None:
-            g["cs"].copy_(cond_sample)
-        g["graph"].replay()
-        eng._mark_use(stream)   # (a repack issued on another stream must wait for this replay's reads of the fragments)
+        replay_graph(eng, g["graph"], lambda stream: refresh(g))
         return g["out"].clone()
 
-    def _graph_denoiser(self, bufs, x32, cond, cond_sample=None):
+    def _graph_denoiser(self, bufs, x32, cond, cond_sample=None, lane=0):
         """One preconditioned UNet evaluation (~160 launches) captured once in a HIP graph and replayed per NFE; sigma is fed
         through a static device slot.  Pays off when the forward is launch-bound (small batches); at B = 64 the host already
         runs ahead of the GPU."""
         g = bufs.get("graph")
-        eng = self.unet._engine(x32.shape[0], x32.shape[2], x32.device, self._lane)
+        eng = self.unet._engine(x32.shape[0], x32.shape[2], x32.device, lane)
         key = (None if cond is None else cond.data_ptr(), None if cond_sample is None else cond_sample.data_ptr(), eng.uid, eng.plan_epoch)
         if g is None or bufs.get("graph_cond") != key:
             slot = th.ones(1, device=x32.device)  # (a valid sigma for the warm-up: sigma = 0 gives c_noise = -inf, NaN activations)
-            self._denoise_static(x32, slot, 0, cond, cond_sample=cond_sample, infer=True)  # warm-up outside capture (plan build, packing)
+            self._denoise_static(x32, slot, 0, cond, cond_sample=cond_sample, infer=True, lane=lane)  # warm-up outside capture (plan build, packing)
             th.cuda.synchronize(x32.device)
             graph = th.cuda.CUDAGraph()
             with th.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self._denoise_static(x32, slot, 0, cond, cond_sample=cond_sample, infer=True)
+                out = self._denoise_static(x32, slot, 0, cond, cond_sample=cond_sample, infer=True, lane=lane)
             g = (graph, slot, out)
             bufs["graph"], bufs["graph_cond"] = g, key
         graph, slot, out = g
         elem = slot.element_size()
 
         def run(sig_ptr):
-            # (packed weights first: see _graph_sample) device-to-device copy of the 4-byte sigma into the captured slot, then replay
-            stream = th.cuda.current_stream(slot.device).cuda_stream
-            eng.repack(stream)
-            _lib_memcpy_d2d(slot.data_ptr(), sig_ptr, elem, stream)
-            graph.replay()
-            eng._mark_use(stream)
+            # device-to-device copy of the 4-byte sigma into the captured slot, then replay
+            replay_graph(eng, graph, lambda stream: _lib_memcpy_d2d(slot.data_ptr(), sig_ptr, elem, stream))
             return out
 
         return run
@@ -584,7 +531,6 @@ class LightningEDM(LightningModule):
         op in the loop is the ``randn_like`` draw of line 207 (``churn_noises[i]``, fp64 unit draws, replace it in tests)."""
         if not eps.is_cuda:
             raise RuntimeError("tqdne_amd samples on MI355X HIP kernels only; got a CPU start state")
-        lib = _lib.load()
         dev = eps.device
         N = self.num_sampling_steps
         sig_cpu = sigmas.detach().to("cpu", th.float32)
@@ -606,45 +552,26 @@ class LightningEDM(LightningModule):
             # the same draws bit for bit where the one-lane plan uses the same tiles (it does at B = 64; a small solo batch takes the
             # small position tile on some levels, engine.SMALL_TILE_WGS, which associates the GroupNorm sums differently: ~1e-6).
             rng_state = th.cuda.get_rng_state(dev) if churn_noises is None else None
-            noises = self._StepNoises(eps.shape, dev, lanes, churn_noises)
-            out = self._run_lanes(eps, sig, cond_sample, cond, lanes, churn=(shat, coef, noises))
-            engs = [e for e in self.unet._engine_cache.values() if e.dev == dev]
-            if engs and engs[0].check_range():   # (the plans are on bf16x3 now: the same draws again)
-                if rng_state is not None:
+
+            def run():
+                if rng_state is not None:   # (a second pass, on bf16x3, integrates the same draws again)
                     th.cuda.set_rng_state(rng_state, dev)
-                return self.sample_stochastically(eps, sigmas, cond_sample, cond, churn_noises, lanes)
-            return out
-        bufs = self._sampler_buffers(eps)
-        if "xh" not in bufs:
-            bufs["xh"] = th.empty_like(bufs["x"])
-        x, xh, xn, d, x32 = bufs["x"], bufs["xh"], bufs["xn"], bufs["d"], bufs["x32"]
-        x.copy_(eps)
-        n = x.numel()
-        stream = th.cuda.current_stream(dev).cuda_stream
-        nsteps = sig.numel() - 1
-        for i in range(nsteps):
-            unit = th.randn_like(x) if churn_noises is None else churn_noises[i].to(device=dev, dtype=th.float64).contiguous()
-            s_hat, s_next = shat.data_ptr() + 4 * i, sig.data_ptr() + 4 * (i + 1)
-            check(lib.tq_heun_churn(_p(x), _p(unit), coef.data_ptr() + 4 * i, float(self.edm.S_noise), _p(xh), _p(x32), n, stream),
-                  "heun churn")
-            den = self._denoise_static(x32, _RawPtr(s_hat), 0, cond, cond_sample=cond_sample, infer=True)
-            check(lib.tq_heun_euler(_p(xh), _p(den), s_hat, s_next, _p(d), _p(xn), _p(x32), n, stream), "heun euler")
-            if i < N - 1:
-                den = self._denoise_static(x32, _RawPtr(s_next), 0, cond, cond_sample=cond_sample, infer=True)
-                check(lib.tq_heun_correct(_p(xh), _p(xn), _p(den), _p(d), s_hat, s_next, _p(x), _p(x32), n, stream), "heun correct")
-            else:
-                x, xn = xn, x
-        out = x.clone()
-        if self.unet._engine(eps.shape[0], eps.shape[2], dev, self._lane).check_range():
-            return self.sample_stochastically(eps, sigmas, cond_sample, cond, churn_noises)  # (the plan is on bf16x3 now)
-        return out
+                noises = self._StepNoises(eps.shape, dev, lanes, churn_noises)
+                return self._run_lanes(eps, sig, cond_sample, cond, lanes, churn=(shat, coef, noises))
+            return retry_on_range(lambda: self._any_plan(dev), run)
+        x = self._sampler_buffers(eps)["x"]
+        if churn_noises is None:
+            noise_of_step = lambda i: th.randn_like(x)
+        else:
+            noise_of_step = lambda i: churn_noises[i].to(device=dev, dtype=th.float64).contiguous()
+        return retry_on_range(self.unet._engine(B, eps.shape[2], dev), lambda: _HeunRun(
+            self, eps, sig, cond_sample, cond, churn=(shat, coef, noise_of_step)).finish().clone())
 
     @th.no_grad()
     def evaluate(self, batch):
         """Evaluate the model on a batch of data (edm.py:232-238)."""
         sample = batch["signal"]
-        cond_sample = batch["cond_signal"] if "cond_signal" in batch else None
-        cond = batch["cond"] if "cond" in batch else None
+        cond_sample, cond = batch.get("cond_signal"), batch.get("cond")
         return self.sample(sample.shape, cond_sample, cond)
 
     def configure_optimizers(self):

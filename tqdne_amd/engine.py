@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from .engine_bwd import BackwardPlan
 from ._lib import (TQ_CONV_DROPOUT, TQ_CONV_EMB, TQ_CONV_GN, TQ_CONV_RES, TQ_CONV_SILU, TQ_CONV_STATS, STAT_SLOT,
-                   TqConvDesc, check)
+                   TqConvDesc, _p, check)
 
 
 def require_device(x: torch.Tensor):
@@ -45,10 +45,6 @@ def _noop_launch(*_args):
 
 def nslots(T: int) -> int:
     return (T + STAT_SLOT - 1) // STAT_SLOT
-
-
-def _p(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 class Act:
@@ -107,6 +103,32 @@ def side_stream(dev, i: int = 1) -> "torch.cuda.Stream":
     if s is None:
         s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return s
+
+
+class lane_fanout:
+    """A batch of ``B`` independent samples as ``lanes`` sub-batches on as many HIP streams: ``streams`` = the current stream and the
+    side streams 1 ... lanes - 1.  Entering makes the side streams wait for the current one, leaving makes the current one wait for
+    them; ``rows(i)`` is lane i's slice of the batch axis, ``cut(t, i)`` its contiguous part of a batch tensor (None stays None)."""
+
+    def __init__(self, dev, B: int, lanes: int):
+        self.h = B // lanes
+        self.main = torch.cuda.current_stream(dev)
+        self.streams = [self.main] + [side_stream(dev, i) for i in range(1, lanes)]
+
+    def rows(self, i: int) -> slice:
+        return slice(i * self.h, (i + 1) * self.h)
+
+    def cut(self, t, i: int):
+        return None if t is None else t[self.rows(i)].contiguous()
+
+    def __enter__(self):
+        for st in self.streams[1:]:
+            st.wait_stream(self.main)
+        return self
+
+    def __exit__(self, *exc):
+        for st in self.streams[1:]:
+            self.main.wait_stream(st)
 
 
 def reserve_side_streams(dev, n: int = 3):

@@ -24,14 +24,10 @@ import torch
 
 from . import _lib
 from ._lib import (PACK_MODE_T, TQ_AMAX_WORDS, TQ_BWD_ACCUM, TQ_BWD_DROPOUT, TQ_BWD_GN, TQ_BWD_SILU, TQ_BWD_STATS, TQ_WFMT_BF16X3, TQ_WFMT_F16_MX6, STAT_SLOT,
-                   TqConvBwdDesc, TqConvDesc, check)
+                   TqConvBwdDesc, TqConvDesc, _p, check)
 
 
 TAIL_WORDS = 2   # floats reserved behind the parameter gradients in a backward plan's flat buffer (see BackwardPlan.run, tail_fill)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 # Weight-gradient launches on a second HIP stream next to the rest of the sweep (see BackwardPlan.run): measured -0.9 ms on the

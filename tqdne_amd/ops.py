@@ -10,15 +10,11 @@ import torch
 
 from . import _lib
 from ._lib import (TQ_CONV_DROPOUT, TQ_CONV_EMB, TQ_CONV_GN, TQ_CONV_RES, TQ_CONV_SILU, TQ_CONV_STATS, STAT_SLOT,
-                   TqConvDesc, check)
+                   TqConvDesc, _p, check)
 
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def nslots(T):
