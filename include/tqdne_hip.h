@@ -533,6 +533,16 @@ int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double ste
                              double inv_bias2_sqrt, double ema_weight, double grad_scale, double decay_factor,
                              const int32_t* skip_flag, hipStream_t stream);
 
+/* torch.optim.RAdam with its defaults (no weight decay, the consistency model's optimizer) on the same chunk table, behind the same
+ * device-side predicate, followed by the same EMA lerp:
+ *   g' = g * grad_scale;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *   rect != 0:  p -= step_size * m * (rect / (sqrt(v) + eps))       rect == 0:  p -= step_size * m
+ * The host, which knows t, forms step_size = lr / (1 - beta1^t) and, where rho_t > 5, rect = r_t * sqrt(1 - beta2^t) in double
+ * (r_t: the variance rectification); rect = 0 selects the un-rectified form of the first steps.  eps is added to sqrt(v) BEFORE
+ * the sqrt(1 - beta2^t) factor, as torch does.  NULL table or n_chunks <= 0: TQ_ERR_ARG, nothing launched. */
+int tq_radam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
+                              double rect, double ema_weight, double grad_scale, const int32_t* skip_flag, hipStream_t stream);
+
 /* ---- signal representation either side of the path (representation.py:41-60, MovingAverageEnvelope) ------- */
 /* x (N, C, T) fp32 NCW -> out (N, 2C, T) fp32: channels [0, C) = x / (env + eps), [C, 2C) = log(env + log_eps) - log(log_eps)/2,
  * env = mean of |x| over [t - W/2, t + (W-1)/2] with zeros outside the signal (np.convolve(..., mode="same")); float64 inside,

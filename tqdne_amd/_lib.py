@@ -192,6 +192,7 @@ _PROTOS = {
     "tq_envelope_inv": (I, [VP, VP, I, I, I, C.c_double, C.c_double, VP]),
     "tq_adam_ema_step": (I, [VP, I] + [C.c_double] * 8 + [VP]),
     "tq_adam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 8 + [VP, VP]),
+    "tq_radam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 7 + [VP, VP]),
     "tq_conv1d_bwd_data": (I, [VP] * 11),
     "tq_conv1d_bwd_weight_workspace": (SZ, [VP]),
     "tq_conv1d_bwd_weight": (I, [VP] * 8 + [SZ, VP]),

@@ -1,7 +1,8 @@
 """Consistency model: drop-in for ``tqdne.consistency_model`` (reference tqdne/consistency_model.py:63-190): forward / sample
 (63-106) and the iCT training step (115-176: teacher at sigma_t without gradient, student at sigma_{t+1}, weighted pseudo-Huber
 distance).  The network is a ``tqdne_amd.UNetModel``; the consistency skip/out scalings are folded into the head-conv epilogue,
-and the raw sigma is the network's timestep (line 77).  Both UNet passes of the training step and its backward are HIP."""
+and the raw sigma is the network's timestep (line 77).  Both UNet passes of the training step and its backward are HIP;
+``step_and_backward`` is the form ``DataParallelTrainer`` drives (flat gradient buffer, bucket hooks, one-launch RAdam + EMA)."""
 
 from __future__ import annotations
 
@@ -18,42 +19,52 @@ from .edm import network_input, retry_on_range
 from .lightning_compat import LightningModule
 
 
+def ict_loss_forward(module, sample, sigmas, timesteps, epsilon, cond, cond_sample, lane=0):
+    """loss = mean(w_t * (sqrt((f(x + s_{t+1} eps, s_{t+1}) - sg[f(x + s_t eps, s_t)])^2 + c^2) - c)),  c = 0.00054 sqrt(dim)
+    (consistency_model.py:140-176) on the plan and buffers of ``lane``.  Returns (loss, the plan that holds the student's activations,
+    d loss / d pred).  The teacher runs first on the same plan: the student's forward overwrites what it left, so only the student
+    has a backward."""
+    engine.require_device(sample)
+    B = sample.shape[0]
+    seed = rng.next_dropout_seed()  # one seed: teacher = student masks
+    train = module.training
+    lib = _lib.load()
+    dev = sample.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    t_sig, s_sig = sigmas[timesteps].float().contiguous(), sigmas[timesteps + 1].float().contiguous()
+    per = sample[0].numel()
+    key = ("ict", tuple(sample.shape), str(dev), lane)
+    bufs = module._scal.get(key)
+    if bufs is None:
+        bufs = dict(xt=torch.empty_like(sample), xs=torch.empty_like(sample), target=torch.empty_like(sample),
+                    dpred=torch.empty_like(sample), loss=torch.empty(1, device=dev))
+        module._scal[key] = bufs
+    epsilon = epsilon.contiguous()
+    # the two noised copies (consistency_model.py:150-160), teacher first (no gradient, same dropout masks as the student)
+    check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(t_sig), _p(bufs["xt"]), B, per, stream), "noise (teacher)")
+    check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(s_sig), _p(bufs["xs"]), B, per, stream), "noise (student)")
+    # (a conditioning signal is concatenated behind both noised copies, consistency_model.py:63-66,111-118; it gets no gradient)
+    bufs["target"].copy_(module._forward_static(bufs["xt"], t_sig, cond, lane=lane, train=train, dropout_seed=seed,
+                                                cond_sample=cond_sample))
+    eng = module.net._engine(B, sample.shape[2], dev, lane)
+    with eng.hold_range_poll():   # (the range guard treats the step as one: a flag the teacher raised is acted on before the next step)
+        pred = module._forward_static(bufs["xs"], s_sig, cond, lane=lane, train=train, dropout_seed=seed, cond_sample=cond_sample)
+    c = 0.00054 * float(np.sqrt(np.prod(sample.shape[2:])))
+    w = (1 / (sigmas[1:] - sigmas[:-1]))[timesteps].float().contiguous()   # (B,) weights: indexing glue, as the schedule
+    check(lib.tq_pseudo_huber_loss(_p(pred), _p(bufs["target"]), _p(w), c, _p(bufs["loss"]), _p(bufs["dpred"]), B, per, stream),
+          "pseudo-Huber loss")
+    # (the plan stays with the caller: a later look-up could find a NEW plan if the bounded cache evicted this one in between)
+    return bufs["loss"][0].clone(), eng, bufs["dpred"]
+
+
 class _ICTLossFn(torch.autograd.Function):
-    """loss = mean(w_t * (sqrt((f(x + s_{t+1} eps, s_{t+1}) - sg[f(x + s_t eps, s_t)])^2 + c^2) - c)),  c = 0.00054 sqrt(dim)."""
+    """``ict_loss_forward`` on lane 0 under autograd."""
 
     @staticmethod
     def forward(ctx, module, sample, sigmas, timesteps, epsilon, cond, cond_sample, *params):
-        engine.require_device(sample)
-        B, nd = sample.shape[0], sample.dim()
-        seed = rng.next_dropout_seed()  # one seed: teacher = student masks
-        train = module.training
-        lib = _lib.load()
-        dev = sample.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        t_sig, s_sig = sigmas[timesteps].float().contiguous(), sigmas[timesteps + 1].float().contiguous()
-        per = sample[0].numel()
-        key = ("ict", tuple(sample.shape), str(dev))
-        bufs = module._scal.get(key)
-        if bufs is None:
-            bufs = dict(xt=torch.empty_like(sample), xs=torch.empty_like(sample), target=torch.empty_like(sample),
-                        dpred=torch.empty_like(sample), loss=torch.empty(1, device=dev))
-            module._scal[key] = bufs
-        epsilon = epsilon.contiguous()
-        # the two noised copies (consistency_model.py:150-160), teacher first (no gradient, same dropout masks as the student)
-        check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(t_sig), _p(bufs["xt"]), B, per, stream), "noise (teacher)")
-        check(lib.tq_axpy_sigma(_p(sample), _p(epsilon), _p(s_sig), _p(bufs["xs"]), B, per, stream), "noise (student)")
-        # (a conditioning signal is concatenated behind both noised copies, consistency_model.py:63-66,111-118; it gets no gradient)
-        bufs["target"].copy_(module._forward_static(bufs["xt"], t_sig, cond, train=train, dropout_seed=seed, cond_sample=cond_sample))
-        pred = module._forward_static(bufs["xs"], s_sig, cond, train=train, dropout_seed=seed, cond_sample=cond_sample)
-        c = 0.00054 * float(np.sqrt(np.prod(sample.shape[2:])))
-        w = (1 / (sigmas[1:] - sigmas[:-1]))[timesteps].float().contiguous()   # (B,) weights: indexing glue, as the schedule
-        check(lib.tq_pseudo_huber_loss(_p(pred), _p(bufs["target"]), _p(w), c, _p(bufs["loss"]), _p(bufs["dpred"]), B, per, stream),
-              "pseudo-Huber loss")
-        ctx.dpred = bufs["dpred"]
-        # (the plan stays with the graph: a later look-up could find a NEW plan if the bounded cache evicted this one in between)
-        ctx.eng = module.net._engine(B, sample.shape[2], dev)
+        loss, ctx.eng, ctx.dpred = ict_loss_forward(module, sample, sigmas, timesteps, epsilon, cond, cond_sample)
         ctx.fwd_id = ctx.eng._fwd_count
-        return bufs["loss"][0].clone()
+        return loss
 
     @staticmethod
     def backward(ctx, gloss):
@@ -137,11 +148,16 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
 
     # ------------------------------------------------------------------ iCT training (consistency_model.py:115-190)
     def _schedule(self):
-        """consistency_model.py:121-138.  ``trainer.max_steps`` / ``global_step`` are Lightning's; without a trainer the
-        attributes ``max_steps`` / ``global_step`` of the module are used."""
-        tr = getattr(self, "trainer", None)
-        max_steps = tr.max_steps if tr is not None else getattr(self, "max_steps", 1)
-        global_step = getattr(self, "global_step", 0)
+        """consistency_model.py:121-138.  Progress comes, in this order, from ``self._dp_progress = (global_step, max_steps)``, which
+        ``DataParallelTrainer(max_steps=...)`` sets before every step (training without Lightning); from Lightning's
+        ``trainer.max_steps`` / ``global_step``; without a trainer from the attributes ``max_steps`` / ``global_step`` of the module."""
+        progress = getattr(self, "_dp_progress", None)
+        if progress is not None:
+            global_step, max_steps = progress
+        else:
+            tr = getattr(self, "trainer", None)
+            max_steps = tr.max_steps if tr is not None else getattr(self, "max_steps", 1)
+            global_step = getattr(self, "global_step", 0)
         prime = np.floor(max_steps / (np.log2(np.floor(self.final_timesteps / self.initial_timesteps)) + 1))
         num = self.initial_timesteps * 2 ** np.floor(global_step / prime)
         num = min(num, self.final_timesteps) + 1
@@ -154,6 +170,15 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         """A single step of training or validation (consistency_model.py:115-176): teacher at sigma_t (no gradient, same
         dropout masks as the student), student at sigma_{t+1}, weighted pseudo-Huber distance.  Both UNet passes and the
         backward are HIP; the schedule, the (B,)-sized draws and the loss on the (B, C, T) outputs are torch glue."""
+        sample, sigmas, pdf, timesteps, epsilon, cond, cond_sample = self._step_inputs(batch)
+        return _ICTLossFn.apply(self, sample, sigmas, timesteps, epsilon, cond, cond_sample, *self.net.parameters())
+
+    def _step_inputs(self, batch):
+        """(sample, sigmas, pdf, timesteps, epsilon, cond, cond_sample) of one training step: the schedule and the two draws of
+        consistency_model.py:121-148, in the reference's order.  The caller holds on to all of them, ``pdf`` included, until the step's
+        launches are enqueued and lets them go in this order, as ``step`` always has: the caching allocator then hands the small
+        temporaries of this and of later calls the same blocks as before, which keeps the launch listings of tools/plan_listing.py
+        comparable line by line."""
         sample = batch["signal"]
         cond_sample, cond = batch.get("cond_signal"), batch.get("cond")
         if cond_sample is not None:
@@ -164,7 +189,23 @@ class LithningConsistencyModel(LightningModule):  # (sic) the reference's class 
         pdf = pdf / pdf.sum()
         timesteps = torch.multinomial(pdf, sample.shape[0], replacement=True)
         epsilon = torch.randn_like(sample)
-        return _ICTLossFn.apply(self, sample.contiguous(), sigmas, timesteps, epsilon, cond, cond_sample, *self.net.parameters())
+        return sample.contiguous(), sigmas, pdf, timesteps, epsilon, cond, cond_sample
+
+    def step_and_backward(self, batch, on_bucket=None, bucket_elems: int = 4 << 20, tail_fill=None):
+        """``step`` + backward in one call, without the autograd round trip: gradients are left in ``p.grad`` of the network's
+        parameters, views of the student plan's flat buffer, which is returned as well: (loss, flat).  One lane.
+        ``on_bucket``: gradient-exchange hook, called as buckets of the flat buffer become final (BackwardPlan.run);
+        ``tail_fill``: extra words of the caller that ride at the end of the last bucket (BackwardPlan.run)."""
+        params = list(self.net.parameters())
+        with torch.no_grad():
+            sample, sigmas, pdf, timesteps, epsilon, cond, cond_sample = self._step_inputs(batch)
+            loss, eng, dpred = ict_loss_forward(self, sample, sigmas, timesteps, epsilon, cond, cond_sample)
+            one = torch.ones((), device=dpred.device)
+            grads = eng.backward(dpred, one, clone=False, on_bucket=on_bucket, bucket_elems=bucket_elems, tail_fill=tail_fill)
+            for p, g in zip(params, grads):
+                if g is not None and (p.grad is None or p.grad.data_ptr() != g.data_ptr()):
+                    p.grad = g
+        return loss, eng._bwd.flat
 
     def training_step(self, batch, batch_idx: int):
         loss = self.step(batch)

@@ -1040,20 +1040,31 @@ extern "C" int tq_concat_scale(const float* x, const float* scale, const float* 
 
 // ------------------------------------------------------------------------------------------------
 // Fused Adam + EMA over the whole model (HBM-bound: reads p, g, m, v [, ema], writes p, m, v [, ema] once; 10 x 62 MB for the
-// paper net).  torch.optim.Adam spends ~8 multi-tensor passes on the same update.
+// paper net).  torch.optim.Adam spends ~8 multi-tensor passes on the same update.  torch.optim.RAdam (the consistency model's
+// optimizer, consistency_model.py:178-190) shares the body.
 // ------------------------------------------------------------------------------------------------
 namespace {
+// RADAM = false: torch.optim.Adam(W); ``denom_scale`` = 1 / sqrt(1 - beta2^t) multiplies sqrt(v) before eps is added.
+// RADAM = true:  torch.optim.RAdam; eps is added to sqrt(v) first and ``denom_scale`` = rect * sqrt(1 - beta2^t) multiplies the
+//                quotient; denom_scale == 0 is the un-rectified form p -= step_size * m (rho_t <= 5, the first steps).
+template <bool RADAM>
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float step_size, float omb1, float b2, float omb2,
-                                      float eps, float ibc2, float gscale, float decay) {
+                                      float eps, float denom_scale, float gscale, float decay) {
     g *= gscale;
-    p *= decay;  // AdamW's decoupled weight decay (1 - lr * wd); 1 for plain Adam
+    if (!RADAM) p *= decay;  // AdamW's decoupled weight decay (1 - lr * wd); 1 for plain Adam
     m = fmaf(omb1, g - m, m);
     v = fmaf(omb2, g * g, b2 * v);
-    p -= step_size * (m / (sqrtf(v) * ibc2 + eps));
+    if (RADAM) {
+        const float upd = step_size * m;
+        p -= denom_scale != 0.f ? upd * (denom_scale / (sqrtf(v) + eps)) : upd;
+    } else {
+        p -= step_size * (m / (sqrtf(v) * denom_scale + eps));
+    }
 }
 
+template <bool RADAM>
 __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __restrict__ chunks, float step_size, float omb1, float b2,
-                                                       float omb2, float eps, float ibc2, float ema_w, float gscale,
+                                                       float omb2, float eps, float denom_scale, float ema_w, float gscale,
                                                        float decay, const int* __restrict__ skip_flag) {
     if (skip_flag && *skip_flag != 0) return;   // (uniform scalar load: the whole launch drops out together)
     const TqAdamChunk c = chunks[blockIdx.x];
@@ -1063,10 +1074,10 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __rest
         const float4 g = *reinterpret_cast<const float4*>(c.g + i);
         float4 m = *reinterpret_cast<const float4*>(c.m + i);
         float4 v = *reinterpret_cast<const float4*>(c.v + i);
-        adam1(p.x, g.x, m.x, v.x, step_size, omb1, b2, omb2, eps, ibc2, gscale, decay);
-        adam1(p.y, g.y, m.y, v.y, step_size, omb1, b2, omb2, eps, ibc2, gscale, decay);
-        adam1(p.z, g.z, m.z, v.z, step_size, omb1, b2, omb2, eps, ibc2, gscale, decay);
-        adam1(p.w, g.w, m.w, v.w, step_size, omb1, b2, omb2, eps, ibc2, gscale, decay);
+        adam1<RADAM>(p.x, g.x, m.x, v.x, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
+        adam1<RADAM>(p.y, g.y, m.y, v.y, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
+        adam1<RADAM>(p.z, g.z, m.z, v.z, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
+        adam1<RADAM>(p.w, g.w, m.w, v.w, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
         *reinterpret_cast<float4*>(c.p + i) = p;
         *reinterpret_cast<float4*>(c.m + i) = m;
         *reinterpret_cast<float4*>(c.v + i) = v;
@@ -1080,7 +1091,7 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __rest
     const int i = n4 + threadIdx.x;
     if (i < c.n) {
         float p = c.p[i], m = c.m[i], v = c.v[i];
-        adam1(p, c.g[i], m, v, step_size, omb1, b2, omb2, eps, ibc2, gscale, decay);
+        adam1<RADAM>(p, c.g[i], m, v, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
         c.p[i] = p; c.m[i] = m; c.v[i] = v;
         if (c.ema) c.ema[i] = fmaf(ema_w, p - c.ema[i], c.ema[i]);
     }
@@ -1092,9 +1103,20 @@ extern "C" int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks,
                                         double decay_factor, const int32_t* skip_flag, hipStream_t stream) {
     if (!chunks || n_chunks < 0) return TQ_ERR_ARG;
     if (n_chunks == 0) return 0;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1),
+    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), (float)eps, (float)inv_bias2_sqrt, (float)ema_weight, (float)grad_scale,
                        (float)decay_factor, reinterpret_cast<const int*>(skip_flag));
+    TQ_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int tq_radam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,
+                                         double eps, double rect, double ema_weight, double grad_scale,
+                                         const int32_t* skip_flag, hipStream_t stream) {
+    if (!chunks || n_chunks <= 0) return TQ_ERR_ARG;
+    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)rect, (float)ema_weight, (float)grad_scale, 1.f,
+                       reinterpret_cast<const int*>(skip_flag));
     TQ_CHECK_LAUNCH();
     return 0;
 }

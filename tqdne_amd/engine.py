@@ -403,6 +403,7 @@ class UNetEngine:
         self.range_flag = shared_range_flag(model, device)
         self._range_host = torch.zeros(1, dtype=torch.int32).pin_memory() if device.type == "cuda" else torch.zeros(1, dtype=torch.int32)
         self._range_evt = None
+        self._range_held = False   # see hold_range_poll
         self._trace = None                  # list: HIP-event pairs around EVERY launch of the next forwards (measurement only)
         self.conv_sites: List[ConvSite] = []
         self.poly_sites: List[Tuple[ConvSite, ConvSite]] = []   # (derived two-phase k = 3 site, the Upsample conv it restates)
@@ -1041,12 +1042,29 @@ class UNetEngine:
             return True
         return False
 
+    def hold_range_poll(self):
+        """Context: forwards inside it do not look at a completed flag copy.  For a training step of several forwards (the consistency
+        model's teacher and student): the plans must not change scheme -- and the flag must not be cleared -- in the middle of a step
+        that the optimizer launch is to drop as a whole; the next step's first forward looks."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def held():
+            self._range_held = True
+            try:
+                yield
+            finally:
+                self._range_held = False
+        return held()
+
     def _range_poll(self, begin: bool):
         """Deferred form for loops that must not synchronise (training steps): the flag is copied to pinned host memory after a
         forward and looked at before a later one, once the copy has completed."""
         if self.scheme != "auto" or torch.cuda.is_current_stream_capturing():
             return
         if begin:
+            if self._range_held:
+                return
             if self._range_evt is not None and self._range_evt.query():
                 self._range_evt = None
                 if int(self._range_host[0]) != 0:

@@ -1,10 +1,14 @@
-"""Fused Adam (+ EMA) for the training step: one HIP launch over the whole model (tq_adam_ema_step).
+"""Fused Adam / RAdam (+ EMA) for the training step: one HIP launch over the whole model (tq_adam_ema_step_guarded,
+tq_radam_ema_step_guarded).
 
 Semantics are ``torch.optim.Adam(params, lr)`` as configured by the reference (tqdne/edm.py:240-251: default betas / eps, no
 weight decay) and, when ``ema_decay`` is given, the reference's EMA callback (tqdne/ema.py:24-28: ``ema.lerp_(p, 1 - decay)``
 after every optimizer step).  The class is a ``torch.optim.Optimizer``: LR schedulers drive ``param_groups[0]["lr"]`` and
 ``state_dict()`` / ``load_state_dict()`` speak torch Adam's format, so the ``optimizer_states`` of a reference checkpoint load.
 Moments (and the EMA copy) live in flat fp32 buffers; ``state[p]["exp_avg"]`` etc. are views of them.
+
+``FusedRAdamEMA`` is the same for ``torch.optim.RAdam(params, lr)``, the consistency model's optimizer (tqdne/consistency_model.py:
+178-190); flat buffers, chunk table, EMA views, version bump and (de)serialisation are ``_FusedFlatOptimizer``'s, shared by both.
 """
 
 from __future__ import annotations
@@ -20,10 +24,13 @@ from . import _lib
 from ._lib import TQ_ADAM_CHUNK, TqAdamChunk, check
 
 
-class FusedAdamEMA(torch.optim.Optimizer):
+class _FusedFlatOptimizer(torch.optim.Optimizer):
+    """What the one-launch optimizers share: flat moment / EMA buffers, the device chunk table, the step's bookkeeping and torch's
+    state format (``step``, ``exp_avg``, ``exp_avg_sq``: Adam's and RAdam's alike).  A subclass supplies ``_launch``."""
+
     def __init__(self, named_params: Iterable[Tuple[str, torch.nn.Parameter]], lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, ema_decay: Optional[float] = None, weight_decay: float = 0.0):
-        """``weight_decay`` > 0 gives torch.optim.AdamW (decoupled decay), the autoencoder's optimizer (autoencoder.py:93-95)."""
+        cls = type(self).__name__
         named = [(n, p) for n, p in named_params if p.requires_grad]
         if not named:
             raise ValueError("no trainable parameters")
@@ -33,12 +40,12 @@ class FusedAdamEMA(torch.optim.Optimizer):
         ps = self.param_groups[0]["params"]
         dev = ps[0].device
         if dev.type != "cuda":
-            raise RuntimeError("FusedAdamEMA updates parameters on the GPU; move the module to cuda first")
+            raise RuntimeError(f"{cls} updates parameters on the GPU; move the module to cuda first")
         self._lib = _lib.load()  # raises when the HIP library is missing: there is no fallback update
         offs, total = [], 0
         for p in ps:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise ValueError("FusedAdamEMA handles contiguous fp32 parameters on one device")
+                raise ValueError(f"{cls} handles contiguous fp32 parameters on one device")
             offs.append(total)
             total += (p.numel() + 63) // 64 * 64  # every tensor starts 256-byte aligned
         self._offs = offs
@@ -79,7 +86,7 @@ class FusedAdamEMA(torch.optim.Optimizer):
                 continue  # like torch: parameters without a gradient are skipped
             g = p.grad
             if g.dtype != torch.float32 or not g.is_contiguous():
-                raise ValueError("FusedAdamEMA needs contiguous fp32 gradients")
+                raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients")
             n = p.numel()
             for s in range(0, n, TQ_ADAM_CHUNK):
                 c = min(TQ_ADAM_CHUNK, n - s)
@@ -101,23 +108,19 @@ class FusedAdamEMA(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0, skip_flag: Optional[torch.Tensor] = None):
         """``skip_flag``: device int32 tensor; when it is non-zero at execution time the launch changes nothing (the range guard
-        of the fp16-range forward scheme, see tq_adam_ema_step_guarded) -- decided on the device, no host synchronisation."""
+        of the fp16-range forward scheme, see tq_adam_ema_step_guarded) -- decided on the device, no host synchronisation; the
+        host-side step count advances all the same."""
         loss = closure() if closure is not None else None
         key = self._key()
         if key != self._table_key:
             self._build_table()
             self._table_key = key
-        g = self.param_groups[0]
-        b1, b2 = g["betas"]
         self._step += 1
         t = self._step
-        step_size = g["lr"] / (1.0 - b1 ** t)
-        ibc2 = 1.0 / math.sqrt(1.0 - b2 ** t)
-        ema_w = 0.0 if self.ema_decay is None else 1.0 - self.ema_decay
-        stream = torch.cuda.current_stream(self._m.device).cuda_stream
-        check(self._lib.tq_adam_ema_step_guarded(self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], ibc2, ema_w,
-                                                 grad_scale, 1.0 - g["lr"] * g["weight_decay"],
-                                                 None if skip_flag is None else skip_flag.data_ptr(), stream), "adam")
+        if self._n_chunks:
+            ema_w = 0.0 if self.ema_decay is None else 1.0 - self.ema_decay
+            stream = torch.cuda.current_stream(self._m.device).cuda_stream
+            self._launch(t, self.param_groups[0], ema_w, grad_scale, None if skip_flag is None else skip_flag.data_ptr(), stream)
         # the kernel wrote the parameters through raw pointers: bump their autograd version counters so that everything keyed
         # on ``p._version`` (the engines' packed MFMA weight fragments, engine.py repack / repack_transposed) sees the update
         torch._C._increment_version(self._updated)
@@ -141,3 +144,42 @@ class FusedAdamEMA(torch.optim.Optimizer):
         for k, v in state_dict["param_groups"][0].items():
             if k in ("lr", "betas", "eps", "initial_lr", "weight_decay"):
                 self.param_groups[0][k] = v
+
+
+class FusedAdamEMA(_FusedFlatOptimizer):
+    """``weight_decay`` > 0 gives torch.optim.AdamW (decoupled decay), the autoencoder's optimizer (autoencoder.py:93-95)."""
+
+    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream):
+        b1, b2 = g["betas"]
+        step_size = g["lr"] / (1.0 - b1 ** t)
+        ibc2 = 1.0 / math.sqrt(1.0 - b2 ** t)
+        check(self._lib.tq_adam_ema_step_guarded(self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], ibc2, ema_w,
+                                                 grad_scale, 1.0 - g["lr"] * g["weight_decay"], skip_ptr, stream), "adam")
+
+
+def radam_scalars(t: int, lr: float, b1: float, b2: float):
+    """(step size lr / (1 - b1^t), rect) of torch.optim.RAdam's step ``t`` in double, as torch's single-tensor path forms them:
+    rect = r_t * sqrt(1 - b2^t) where rho_t > 5, else 0 = the un-rectified update p -= step_size * m."""
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    rho_inf = 2.0 / (1.0 - b2) - 1.0
+    rho_t = rho_inf - 2.0 * t * (b2 ** t) / bc2
+    rect = 0.0
+    if rho_t > 5.0:
+        rect = math.sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t)) * math.sqrt(bc2)
+    return lr / bc1, rect
+
+
+class FusedRAdamEMA(_FusedFlatOptimizer):
+    """torch.optim.RAdam with its defaults (weight_decay=0, decoupled_weight_decay=False, maximize=False) + the EMA lerp."""
+
+    def __init__(self, named_params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, ema_decay: Optional[float] = None,
+                 weight_decay: float = 0.0):
+        if weight_decay != 0:
+            raise ValueError("FusedRAdamEMA implements torch.optim.RAdam without weight decay (the consistency model's optimizer)")
+        super().__init__(named_params, lr=lr, betas=betas, eps=eps, ema_decay=ema_decay, weight_decay=0.0)
+
+    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream):
+        b1, b2 = g["betas"]
+        step_size, rect = radam_scalars(t, g["lr"], b1, b2)
+        check(self._lib.tq_radam_ema_step_guarded(self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], rect, ema_w,
+                                                  grad_scale, skip_ptr, stream), "radam")

@@ -1,7 +1,8 @@
-"""Data-parallel training loop for the EDM module: stands where Lightning's fit loop + DDPStrategy stand in the
-reference (experiments/train_1d_edm.py:34-70): one process per GPU, identical replicas, the batch is
+"""Data-parallel training loop for the EDM module, the autoencoder and the consistency model: stands where Lightning's fit loop +
+DDPStrategy stand in the reference (experiments/train_1d_edm.py:34-70): one process per GPU, identical replicas, the batch is
 sharded by rank, gradients are summed with RCCL all-reduce over xGMI (torch.distributed backend "nccl") and divided
-by the world size, then every rank applies the same Adam + per-step cosine LR update (edm.py:240-251).
+by the world size, then every rank applies the same Adam + per-step cosine LR update (edm.py:240-251) -- or, for the consistency
+model, the same RAdam update without a scheduler (consistency_model.py:178-190).
 
 The exchange is overlapped with the backward, the way torch's DDP reducer does it for the reference: the backward plan lays
 the flat gradient buffer out in the order its reverse sweep finalises the gradients (head, output blocks, middle block,
@@ -72,11 +73,15 @@ class _Done:
 
 class DataParallelTrainer:
     def __init__(self, module, world_size: int = 1, bucket_bytes: int = 16 << 20, ema_decay=None, fused_optimizer=None,
-                 overlap: bool = True, process_group=None, force_exchange: bool = False):
-        """``force_exchange``: issue the collectives with ONE rank too (a sum over one rank is the identity: the self-test of the
+                 overlap: bool = True, process_group=None, force_exchange: bool = False, max_steps=None):
+        """``max_steps``: length of the run for modules whose training step depends on its progress (the consistency model's iCT
+        schedule, which under Lightning reads ``trainer.max_steps`` / ``global_step``): when given, ``module._dp_progress =
+        (steps done so far, max_steps)`` is set before every ``step_and_backward``.  None: nothing is published.
+        ``force_exchange``: issue the collectives with ONE rank too (a sum over one rank is the identity: the self-test of the
         RCCL path on a 1-GPU box -- communicator, RCCL's stream behind the sweep's launches, the waits in front of the optimizer).
         ``ema_decay``: keep the EMA weights of the reference's EMA callback (tqdne/ema.py; 0.999 in the reference's runs).
-        ``fused_optimizer``: one-launch Adam (+ EMA) instead of torch.optim.Adam; default: on GPUs.
+        ``fused_optimizer``: one-launch Adam / AdamW / RAdam (+ EMA) instead of torch's; default: on GPUs.  An optimizer of any
+        other class is kept as the module configured it (with the foreach-lerp EMA).
         ``overlap``: issue each gradient bucket's all-reduce from inside the backward sweep (default) instead of after it.
         ``bucket_bytes``: 16 MB = 4 buckets over the paper UNet's 62 MB of gradients (xGMI rings are per-link bound: few,
         large messages; the first bucket leaves after the output blocks' half of the sweep)."""
@@ -86,21 +91,35 @@ class DataParallelTrainer:
         self.overlap = overlap
         self.exchange = world_size > 1 or force_exchange
         cfg = module.configure_optimizers()
-        self.optimizer = cfg["optimizer"]
-        self.scheduler = cfg["lr_scheduler"]["scheduler"]
+        if isinstance(cfg, torch.optim.Optimizer):   # a bare optimizer (the consistency model's RAdam): no LR scheduler
+            self.optimizer, self.scheduler = cfg, None
+        else:
+            self.optimizer = cfg["optimizer"]
+            self.scheduler = cfg["lr_scheduler"]["scheduler"]
         on_gpu = next(module.parameters()).device.type == "cuda"
         self.fused = on_gpu if fused_optimizer is None else fused_optimizer
         self.ema_decay = ema_decay
+        self.max_steps = max_steps
+        self.steps_done = 0
         self._ema = None
+        # (exact classes: a subclass may change the update)
+        if self.fused and type(self.optimizer) not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.RAdam):
+            self.fused = False
         if self.fused:
-            from .optim import FusedAdamEMA
+            from .optim import FusedAdamEMA, FusedRAdamEMA
             g = self.optimizer.param_groups[0]
-            wd = g.get("weight_decay", 0.0) if isinstance(self.optimizer, torch.optim.AdamW) else 0.0
-            self.optimizer = FusedAdamEMA(module.named_parameters(), lr=g["lr"], betas=g["betas"], eps=g["eps"],
-                                          ema_decay=ema_decay, weight_decay=wd)
-            op = module.optimizer_params
-            self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=op["max_steps"],
-                                                                        eta_min=op["eta_min"])
+            named = self._named_optimized(g["params"])
+            if isinstance(self.optimizer, torch.optim.RAdam):
+                self.optimizer = FusedRAdamEMA(named, lr=g["lr"], betas=g["betas"], eps=g["eps"], ema_decay=ema_decay,
+                                               weight_decay=g.get("weight_decay", 0.0))
+            else:
+                wd = g.get("weight_decay", 0.0) if isinstance(self.optimizer, torch.optim.AdamW) else 0.0
+                self.optimizer = FusedAdamEMA(named, lr=g["lr"], betas=g["betas"], eps=g["eps"], ema_decay=ema_decay,
+                                              weight_decay=wd)
+            if self.scheduler is not None:
+                op = module.optimizer_params
+                self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=op["max_steps"],
+                                                                            eta_min=op["eta_min"])
         elif ema_decay is not None:
             self._ema = {n: p.detach().clone() for n, p in module.named_parameters() if p.requires_grad}
         self.bucket_elems = max(1, bucket_bytes // 4)
@@ -110,6 +129,26 @@ class DataParallelTrainer:
         self.last_bucket_sizes = []   # elements of each bucket exchanged by the last step, in issue order (diagnostics / tests)
         if self.exchange:
             self._broadcast_parameters()
+
+    def _named_optimized(self, params):
+        """(name, parameter) of the module's parameters, in the module's order; the configured optimizer must hold them all (both
+        EDM's ``self.parameters()`` and the consistency model's ``self.net.parameters()`` do)."""
+        named = list(self.module.named_parameters())
+        held = {id(p) for p in params}
+        missing = [n for n, p in named if p.requires_grad and id(p) not in held]
+        if missing:
+            raise ValueError(f"the module's optimizer leaves out trainable parameters ({missing[0]}, ...): not a case the fused "
+                             "optimizer handles; pass fused_optimizer=False")
+        return named
+
+    def _network(self):
+        """the module's 1-D network, whose range-guard flag the optimizer launch is predicated on: ``unet`` (EDM) or ``net`` (the
+        consistency model); None for modules without one (autoencoder) and for dims=2 networks"""
+        for name in ("unet", "net"):
+            net = getattr(self.module, name, None)
+            if net is not None:
+                return net if getattr(net, "dims", 1) == 1 else None
+        return None
 
     # ------------------------------------------------------------------ exchange
     def _broadcast_parameters(self):
@@ -170,6 +209,8 @@ class DataParallelTrainer:
                 self._skip_fill(words)
                 tail.append(words)
                 self.last_tail_words = words.numel()
+        if self.max_steps is not None:
+            self.module._dp_progress = (self.steps_done, self.max_steps)
         if tail is not None:
             loss, flat = self.module.step_and_backward(batch, on_bucket=hook, bucket_elems=self.bucket_elems, tail_fill=tail_fill)
         elif self._hooked:
@@ -204,15 +245,17 @@ class DataParallelTrainer:
                 with torch.no_grad():
                     named = dict(self.module.named_parameters())
                     torch._foreach_lerp_(tuple(self._ema.values()), tuple(named[n] for n in self._ema), 1 - self.ema_decay)
-        self.scheduler.step()
+        if self.scheduler is not None:
+            self.scheduler.step()
+        self.steps_done += 1
         return loss
 
     AGREE_EVERY = 64   # steps between the (host-synchronous) checks whether every rank has left the fp16-range scheme
 
     def _local_range_flag(self):
         """(device int32[1] range-guard flag of this rank's model | None, is this rank still on the fp16-range scheme?)"""
-        unet = getattr(self.module, "unet", None)
-        if not self.fused or unet is None or getattr(unet, "dims", 1) != 1:
+        unet = self._network()
+        if not self.fused or unet is None:
             return None, False
         dev = next(self.module.parameters()).device
         from .engine import shared_range_flag
