@@ -543,6 +543,31 @@ int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double ste
 int tq_radam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
                               double rect, double ema_weight, double grad_scale, const int32_t* skip_flag, hipStream_t stream);
 
+/* Gradient clipping and gradient-norm tracking inside the one-launch update (what pl.Trainer's gradient_clip_val /
+ * gradient_clip_algorithm do for the reference): decided on the device, no host synchronisation, no extra pass over parameters or
+ * moments.  Two small launches in front of the update form the norm over the optimizer's own chunk table:
+ *   tq_grad_sumsq:     one workgroup per chunk, reads g only: partials[i] = sum of g^2 over chunk i (a DEVICE array of n_chunks
+ *     doubles); squares and sums in fp64 from the fp32 values, in a fixed order (no atomics): the same gradients give the same bits.
+ *   tq_grad_clip_coef: one workgroup adds the partials in a fixed order in fp64 (any n_chunks) and writes two DEVICE floats,
+ *       out[0] = norm = (float)(grad_scale * sqrt(total))            the norm of the scaled gradient, before clipping
+ *       out[1] = coef = min(1, max_norm / (norm + 1e-6f))            in fp32, as torch.nn.utils.clip_grad_norm_ forms it
+ *     max_norm <= 0: coef = 1 (tracking only).  Non-finite norms are not special: a NaN norm gives a NaN coefficient, as in torch
+ *     (error_if_nonfinite=False).
+ * The _clipped entry points are the _guarded ones with two more arguments; per element, every step rounded to fp32 in torch's order,
+ *   g' = g * grad_scale;   clip_coef != NULL: g' *= *clip_coef;   clip_value > 0: g' = clamp(g', -clip_value, clip_value)
+ * and the update goes on with g' as above (a NaN stays a NaN through the clamp, as in clip_grad_value_).  `clip_coef` is a DEVICE
+ * float (out + 1 of tq_grad_clip_coef), read once per workgroup like `skip_flag`; NULL with clip_value == 0 runs the kernel of the
+ * _guarded entry point.  A raised `skip_flag` still drops the whole update.
+ * NULL table / partials / out, n_chunks <= 0 or a negative clip_value: TQ_ERR_ARG, nothing launched. */
+int tq_grad_sumsq(const TqAdamChunk* chunks, int n_chunks, double* partials, hipStream_t stream);
+int tq_grad_clip_coef(const double* partials, int n_chunks, double grad_scale, double max_norm, float* out, hipStream_t stream);
+int tq_adam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
+                             double inv_bias2_sqrt, double ema_weight, double grad_scale, double decay_factor,
+                             const int32_t* skip_flag, const float* clip_coef, double clip_value, hipStream_t stream);
+int tq_radam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
+                              double rect, double ema_weight, double grad_scale, const int32_t* skip_flag, const float* clip_coef,
+                              double clip_value, hipStream_t stream);
+
 /* ---- signal representation either side of the path (representation.py:41-60, MovingAverageEnvelope) ------- */
 /* x (N, C, T) fp32 NCW -> out (N, 2C, T) fp32: channels [0, C) = x / (env + eps), [C, 2C) = log(env + log_eps) - log(log_eps)/2,
  * env = mean of |x| over [t - W/2, t + (W-1)/2] with zeros outside the signal (np.convolve(..., mode="same")); float64 inside,

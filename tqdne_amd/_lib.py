@@ -193,6 +193,10 @@ _PROTOS = {
     "tq_adam_ema_step": (I, [VP, I] + [C.c_double] * 8 + [VP]),
     "tq_adam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 8 + [VP, VP]),
     "tq_radam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 7 + [VP, VP]),
+    "tq_adam_ema_step_clipped": (I, [VP, I] + [C.c_double] * 8 + [VP, VP, C.c_double, VP]),
+    "tq_radam_ema_step_clipped": (I, [VP, I] + [C.c_double] * 7 + [VP, VP, C.c_double, VP]),
+    "tq_grad_sumsq": (I, [VP, I, VP, VP]),
+    "tq_grad_clip_coef": (I, [VP, I, C.c_double, C.c_double, VP, VP]),
     "tq_conv1d_bwd_data": (I, [VP] * 11),
     "tq_conv1d_bwd_weight_workspace": (SZ, [VP]),
     "tq_conv1d_bwd_weight": (I, [VP] * 8 + [SZ, VP]),

@@ -1041,16 +1041,23 @@ extern "C" int tq_concat_scale(const float* x, const float* scale, const float* 
 // ------------------------------------------------------------------------------------------------
 // Fused Adam + EMA over the whole model (HBM-bound: reads p, g, m, v [, ema], writes p, m, v [, ema] once; 10 x 62 MB for the
 // paper net).  torch.optim.Adam spends ~8 multi-tensor passes on the same update.  torch.optim.RAdam (the consistency model's
-// optimizer, consistency_model.py:178-190) shares the body.
+// optimizer, consistency_model.py:178-190) shares the body, and so does the clipped update (pl.Trainer's gradient_clip_val): the norm of
+// the gradient comes from two small launches over the same chunk table, the coefficient / the clamp is applied inside the update.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // RADAM = false: torch.optim.Adam(W); ``denom_scale`` = 1 / sqrt(1 - beta2^t) multiplies sqrt(v) before eps is added.
 // RADAM = true:  torch.optim.RAdam; eps is added to sqrt(v) first and ``denom_scale`` = rect * sqrt(1 - beta2^t) multiplies the
 //                quotient; denom_scale == 0 is the un-rectified form p -= step_size * m (rho_t <= 5, the first steps).
-template <bool RADAM>
+template <bool RADAM, bool CLIP>
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float step_size, float omb1, float b2, float omb2,
-                                      float eps, float denom_scale, float gscale, float decay) {
+                                      float eps, float denom_scale, float gscale, float decay, float coef, float clip_v) {
     g *= gscale;
+    if (CLIP) {
+        // torch's order, every step rounded to fp32: clip_grad_norm_'s g.mul_(coef) (coef = 1 without a norm), then clip_grad_value_'s
+        // clamp (clip_v = +inf without one); a NaN fails both comparisons and stays a NaN
+        g *= coef;
+        g = g < -clip_v ? -clip_v : (g > clip_v ? clip_v : g);
+    }
     if (!RADAM) p *= decay;  // AdamW's decoupled weight decay (1 - lr * wd); 1 for plain Adam
     m = fmaf(omb1, g - m, m);
     v = fmaf(omb2, g * g, b2 * v);
@@ -1062,11 +1069,14 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
     }
 }
 
-template <bool RADAM>
+// CLIP = false is the kernel of the _guarded entry points: no load of the coefficient, no extra arithmetic.
+template <bool RADAM, bool CLIP>
 __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __restrict__ chunks, float step_size, float omb1, float b2,
                                                        float omb2, float eps, float denom_scale, float ema_w, float gscale,
-                                                       float decay, const int* __restrict__ skip_flag) {
+                                                       float decay, const int* __restrict__ skip_flag,
+                                                       const float* __restrict__ clip_coef, float clip_v) {
     if (skip_flag && *skip_flag != 0) return;   // (uniform scalar load: the whole launch drops out together)
+    const float coef = (CLIP && clip_coef) ? *clip_coef : 1.f;   // (uniform as well; 1: the multiplication is exact)
     const TqAdamChunk c = chunks[blockIdx.x];
     const int n4 = c.n & ~3;
     for (int i = threadIdx.x * 4; i < n4; i += 256 * 4) {
@@ -1074,10 +1084,10 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __rest
         const float4 g = *reinterpret_cast<const float4*>(c.g + i);
         float4 m = *reinterpret_cast<const float4*>(c.m + i);
         float4 v = *reinterpret_cast<const float4*>(c.v + i);
-        adam1<RADAM>(p.x, g.x, m.x, v.x, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
-        adam1<RADAM>(p.y, g.y, m.y, v.y, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
-        adam1<RADAM>(p.z, g.z, m.z, v.z, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
-        adam1<RADAM>(p.w, g.w, m.w, v.w, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
+        adam1<RADAM, CLIP>(p.x, g.x, m.x, v.x, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay, coef, clip_v);
+        adam1<RADAM, CLIP>(p.y, g.y, m.y, v.y, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay, coef, clip_v);
+        adam1<RADAM, CLIP>(p.z, g.z, m.z, v.z, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay, coef, clip_v);
+        adam1<RADAM, CLIP>(p.w, g.w, m.w, v.w, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay, coef, clip_v);
         *reinterpret_cast<float4*>(c.p + i) = p;
         *reinterpret_cast<float4*>(c.m + i) = m;
         *reinterpret_cast<float4*>(c.v + i) = v;
@@ -1091,9 +1101,71 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(const TqAdamChunk* __rest
     const int i = n4 + threadIdx.x;
     if (i < c.n) {
         float p = c.p[i], m = c.m[i], v = c.v[i];
-        adam1<RADAM>(p, c.g[i], m, v, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay);
+        adam1<RADAM, CLIP>(p, c.g[i], m, v, step_size, omb1, b2, omb2, eps, denom_scale, gscale, decay, coef, clip_v);
         c.p[i] = p; c.m[i] = m; c.v[i] = v;
         if (c.ema) c.ema[i] = fmaf(ema_w, p - c.ema[i], c.ema[i]);
+    }
+}
+
+template <bool RADAM>
+int launch_adam_ema(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
+                    double denom_scale, double ema_weight, double grad_scale, double decay_factor, const int32_t* skip_flag,
+                    const float* clip_coef, double clip_value, hipStream_t stream) {
+    const bool clip = clip_coef != nullptr || clip_value > 0.0;
+    const float clip_v = clip_value > 0.0 ? (float)clip_value : INFINITY;
+    auto kernel = clip ? adam_ema_kernel<RADAM, true> : adam_ema_kernel<RADAM, false>;
+    hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                       (float)denom_scale, (float)ema_weight, (float)grad_scale, (float)decay_factor,
+                       reinterpret_cast<const int*>(skip_flag), clip_coef, clip_v);
+    TQ_CHECK_LAUNCH();
+    return 0;
+}
+
+// Sum of squares of one chunk's gradients: 256 threads, each at most 4 float4 of the 4096 elements, squares and sums in fp64; the
+// 64 lanes of a wave fold by shuffles, the 4 waves through LDS, always in the same order (no atomics: the same input, the same bits).
+__device__ __forceinline__ double block_sum_256(double acc, double* lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (lds[0] + lds[1]) + (lds[2] + lds[3]);   // (every thread; thread 0 stores)
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const TqAdamChunk* __restrict__ chunks, double* __restrict__ partials) {
+    __shared__ double lds[4];
+    const TqAdamChunk c = chunks[blockIdx.x];
+    const int n4 = c.n & ~3;
+    double acc = 0.0;
+    for (int i = threadIdx.x * 4; i < n4; i += 256 * 4) {
+        const float4 g = *reinterpret_cast<const float4*>(c.g + i);
+        const double x = g.x, y = g.y, z = g.z, w = g.w;
+        acc += (x * x + y * y) + (z * z + w * w);
+    }
+    const int i = n4 + threadIdx.x;
+    if (i < c.n) {
+        const double x = c.g[i];
+        acc += x * x;
+    }
+    const double total = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// One workgroup: thread t adds partials t, t + 256, ... in that order, then the same fold.  out[0] = norm, out[1] = coefficient.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ partials, int n, double grad_scale,
+                                                             float max_norm, float* __restrict__ out) {
+    __shared__ double lds[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double total = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) {
+        const float norm = (float)(grad_scale * sqrt(total));
+        float coef = 1.f;
+        if (max_norm > 0.f) {   // torch.nn.utils.clip_grad_norm_ in fp32; a NaN norm gives a NaN coefficient (c > 1 is false)
+            const float cc = max_norm / (norm + 1e-6f);
+            coef = cc > 1.f ? 1.f : cc;
+        }
+        out[0] = norm;
+        out[1] = coef;
     }
 }
 }  // namespace
@@ -1103,22 +1175,16 @@ extern "C" int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks,
                                         double decay_factor, const int32_t* skip_flag, hipStream_t stream) {
     if (!chunks || n_chunks < 0) return TQ_ERR_ARG;
     if (n_chunks == 0) return 0;
-    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)inv_bias2_sqrt, (float)ema_weight, (float)grad_scale,
-                       (float)decay_factor, reinterpret_cast<const int*>(skip_flag));
-    TQ_CHECK_LAUNCH();
-    return 0;
+    return launch_adam_ema<false>(chunks, n_chunks, step_size, beta1, beta2, eps, inv_bias2_sqrt, ema_weight, grad_scale, decay_factor,
+                                  skip_flag, nullptr, 0.0, stream);
 }
 
 extern "C" int tq_radam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,
                                          double eps, double rect, double ema_weight, double grad_scale,
                                          const int32_t* skip_flag, hipStream_t stream) {
     if (!chunks || n_chunks <= 0) return TQ_ERR_ARG;
-    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(n_chunks), dim3(256), 0, stream, chunks, (float)step_size, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)rect, (float)ema_weight, (float)grad_scale, 1.f,
-                       reinterpret_cast<const int*>(skip_flag));
-    TQ_CHECK_LAUNCH();
-    return 0;
+    return launch_adam_ema<true>(chunks, n_chunks, step_size, beta1, beta2, eps, rect, ema_weight, grad_scale, 1.0, skip_flag, nullptr,
+                                 0.0, stream);
 }
 
 extern "C" int tq_adam_ema_step(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
@@ -1126,6 +1192,39 @@ extern "C" int tq_adam_ema_step(const TqAdamChunk* chunks, int n_chunks, double 
                                 hipStream_t stream) {
     return tq_adam_ema_step_guarded(chunks, n_chunks, step_size, beta1, beta2, eps, inv_bias2_sqrt, ema_weight, grad_scale,
                                     decay_factor, nullptr, stream);
+}
+
+extern "C" int tq_adam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,
+                                        double eps, double inv_bias2_sqrt, double ema_weight, double grad_scale,
+                                        double decay_factor, const int32_t* skip_flag, const float* clip_coef, double clip_value,
+                                        hipStream_t stream) {
+    if (!chunks || n_chunks <= 0 || !(clip_value >= 0.0)) return TQ_ERR_ARG;
+    return launch_adam_ema<false>(chunks, n_chunks, step_size, beta1, beta2, eps, inv_bias2_sqrt, ema_weight, grad_scale, decay_factor,
+                                  skip_flag, clip_coef, clip_value, stream);
+}
+
+extern "C" int tq_radam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,
+                                         double eps, double rect, double ema_weight, double grad_scale, const int32_t* skip_flag,
+                                         const float* clip_coef, double clip_value, hipStream_t stream) {
+    if (!chunks || n_chunks <= 0 || !(clip_value >= 0.0)) return TQ_ERR_ARG;
+    return launch_adam_ema<true>(chunks, n_chunks, step_size, beta1, beta2, eps, rect, ema_weight, grad_scale, 1.0, skip_flag,
+                                 clip_coef, clip_value, stream);
+}
+
+extern "C" int tq_grad_sumsq(const TqAdamChunk* chunks, int n_chunks, double* partials, hipStream_t stream) {
+    if (!chunks || !partials || n_chunks <= 0) return TQ_ERR_ARG;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, stream, chunks, partials);
+    TQ_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int tq_grad_clip_coef(const double* partials, int n_chunks, double grad_scale, double max_norm, float* out,
+                                 hipStream_t stream) {
+    if (!partials || !out || n_chunks <= 0) return TQ_ERR_ARG;
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, stream, partials, n_chunks, grad_scale,
+                       max_norm > 0.0 ? (float)max_norm : 0.f, out);
+    TQ_CHECK_LAUNCH();
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

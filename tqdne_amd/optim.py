@@ -1,5 +1,6 @@
 """Fused Adam / RAdam (+ EMA) for the training step: one HIP launch over the whole model (tq_adam_ema_step_guarded,
-tq_radam_ema_step_guarded).
+tq_radam_ema_step_guarded), optionally with gradient clipping / gradient-norm tracking decided on the device (tq_grad_sumsq,
+tq_grad_clip_coef, tq_*_ema_step_clipped).
 
 Semantics are ``torch.optim.Adam(params, lr)`` as configured by the reference (tqdne/edm.py:240-251: default betas / eps, no
 weight decay) and, when ``ema_decay`` is given, the reference's EMA callback (tqdne/ema.py:24-28: ``ema.lerp_(p, 1 - decay)``
@@ -26,7 +27,8 @@ from ._lib import TQ_ADAM_CHUNK, TqAdamChunk, check
 
 class _FusedFlatOptimizer(torch.optim.Optimizer):
     """What the one-launch optimizers share: flat moment / EMA buffers, the device chunk table, the step's bookkeeping and torch's
-    state format (``step``, ``exp_avg``, ``exp_avg_sq``: Adam's and RAdam's alike).  A subclass supplies ``_launch``."""
+    state format (``step``, ``exp_avg``, ``exp_avg_sq``: Adam's and RAdam's alike), gradient clipping / norm tracking in front of
+    the launch.  A subclass supplies ``_launch``."""
 
     def __init__(self, named_params: Iterable[Tuple[str, torch.nn.Parameter]], lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, ema_decay: Optional[float] = None, weight_decay: float = 0.0):
@@ -64,6 +66,8 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
                                  exp_avg_sq=self._v[o:o + n].view_as(p))
         self._table = None
         self._table_key = None
+        self._norm_buf = None        # (fp64 partials per chunk, [norm, coefficient]) of the current table, made on first use
+        self.last_grad_norm = None   # device fp32 scalar once a step has formed the norm
 
     # ------------------------------------------------------------------ EMA
     def ema_state(self) -> "OrderedDict[str, torch.Tensor]":
@@ -98,6 +102,7 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self._table = host.to(self._m.device)
         self._n_chunks = len(rows)
+        self._norm_buf = None
         self._updated = [p for p in ps if p.grad is not None]
 
     def _key(self):
@@ -106,10 +111,26 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ step
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, skip_flag: Optional[torch.Tensor] = None):
+    def step(self, closure=None, grad_scale: float = 1.0, skip_flag: Optional[torch.Tensor] = None,
+             max_grad_norm: Optional[float] = None, clip_value: Optional[float] = None, track_grad_norm: bool = False):
         """``skip_flag``: device int32 tensor; when it is non-zero at execution time the launch changes nothing (the range guard
         of the fp16-range forward scheme, see tq_adam_ema_step_guarded) -- decided on the device, no host synchronisation; the
-        host-side step count advances all the same."""
+        host-side step count advances all the same.
+
+        ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` on the scaled gradients ``grad_scale * g``,
+        inside the launch: two small launches in front of it form the total 2-norm (fp64 partial sums per chunk, fixed order) and
+        the coefficient ``min(1, max_grad_norm / (norm + 1e-6))`` on the device; the update multiplies it in.  ``p.grad`` itself is
+        left as it was.  ``clip_value``: ``clip_grad_value_`` the same way (a clamp in the launch, no extra launch).  One of the
+        two at most, like Lightning's ``gradient_clip_algorithm``.  ``track_grad_norm``: form the norm without clipping.
+        Whenever the norm is formed, ``last_grad_norm`` is a device fp32 scalar holding it (of the scaled gradient, before
+        clipping; a view of a buffer the next such step overwrites; never synchronised here).  ``skip_flag`` keeps its meaning: a
+        raised flag drops the whole update, and the norm of such a step may be inf.  With none of the three given the step issues
+        exactly the launch it always did."""
+        if max_grad_norm is not None and clip_value is not None:
+            raise ValueError("max_grad_norm and clip_value are alternatives (gradient_clip_algorithm 'norm' or 'value'): give one")
+        for name, val in (("max_grad_norm", max_grad_norm), ("clip_value", clip_value)):
+            if val is not None and not val > 0:
+                raise ValueError(f"{name} must be positive, got {val!r}")
         loss = closure() if closure is not None else None
         key = self._key()
         if key != self._table_key:
@@ -120,7 +141,22 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         if self._n_chunks:
             ema_w = 0.0 if self.ema_decay is None else 1.0 - self.ema_decay
             stream = torch.cuda.current_stream(self._m.device).cuda_stream
-            self._launch(t, self.param_groups[0], ema_w, grad_scale, None if skip_flag is None else skip_flag.data_ptr(), stream)
+            clip = None
+            if max_grad_norm is not None or track_grad_norm:
+                if self._norm_buf is None:
+                    self._norm_buf = (torch.empty(self._n_chunks, dtype=torch.float64, device=self._m.device),
+                                      torch.empty(2, dtype=torch.float32, device=self._m.device))
+                partials, out = self._norm_buf
+                check(self._lib.tq_grad_sumsq(self._table.data_ptr(), self._n_chunks, partials.data_ptr(), stream), "grad_sumsq")
+                check(self._lib.tq_grad_clip_coef(partials.data_ptr(), self._n_chunks, grad_scale, max_grad_norm or 0.0,
+                                                  out.data_ptr(), stream), "grad_clip_coef")
+                self.last_grad_norm = out[0]
+                if max_grad_norm is not None:
+                    clip = (out.data_ptr() + 4, 0.0)
+            if clip_value is not None:
+                clip = (None, float(clip_value))
+            self._launch(t, self.param_groups[0], ema_w, grad_scale, None if skip_flag is None else skip_flag.data_ptr(), stream,
+                         clip)
         # the kernel wrote the parameters through raw pointers: bump their autograd version counters so that everything keyed
         # on ``p._version`` (the engines' packed MFMA weight fragments, engine.py repack / repack_transposed) sees the update
         torch._C._increment_version(self._updated)
@@ -149,12 +185,16 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
 class FusedAdamEMA(_FusedFlatOptimizer):
     """``weight_decay`` > 0 gives torch.optim.AdamW (decoupled decay), the autoencoder's optimizer (autoencoder.py:93-95)."""
 
-    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream):
+    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream, clip=None):
         b1, b2 = g["betas"]
         step_size = g["lr"] / (1.0 - b1 ** t)
         ibc2 = 1.0 / math.sqrt(1.0 - b2 ** t)
-        check(self._lib.tq_adam_ema_step_guarded(self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], ibc2, ema_w,
-                                                 grad_scale, 1.0 - g["lr"] * g["weight_decay"], skip_ptr, stream), "adam")
+        args = (self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], ibc2, ema_w, grad_scale,
+                1.0 - g["lr"] * g["weight_decay"], skip_ptr)
+        if clip is None:
+            check(self._lib.tq_adam_ema_step_guarded(*args, stream), "adam")
+        else:   # (device pointer of the norm-clipping coefficient | None, clip_value | 0.0)
+            check(self._lib.tq_adam_ema_step_clipped(*args, clip[0], clip[1], stream), "adam (clipped)")
 
 
 def radam_scalars(t: int, lr: float, b1: float, b2: float):
@@ -178,8 +218,11 @@ class FusedRAdamEMA(_FusedFlatOptimizer):
             raise ValueError("FusedRAdamEMA implements torch.optim.RAdam without weight decay (the consistency model's optimizer)")
         super().__init__(named_params, lr=lr, betas=betas, eps=eps, ema_decay=ema_decay, weight_decay=0.0)
 
-    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream):
+    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream, clip=None):
         b1, b2 = g["betas"]
         step_size, rect = radam_scalars(t, g["lr"], b1, b2)
-        check(self._lib.tq_radam_ema_step_guarded(self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], rect, ema_w,
-                                                  grad_scale, skip_ptr, stream), "radam")
+        args = (self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], rect, ema_w, grad_scale, skip_ptr)
+        if clip is None:
+            check(self._lib.tq_radam_ema_step_guarded(*args, stream), "radam")
+        else:
+            check(self._lib.tq_radam_ema_step_clipped(*args, clip[0], clip[1], stream), "radam (clipped)")

@@ -73,8 +73,19 @@ class _Done:
 
 class DataParallelTrainer:
     def __init__(self, module, world_size: int = 1, bucket_bytes: int = 16 << 20, ema_decay=None, fused_optimizer=None,
-                 overlap: bool = True, process_group=None, force_exchange: bool = False, max_steps=None):
-        """``max_steps``: length of the run for modules whose training step depends on its progress (the consistency model's iCT
+                 overlap: bool = True, process_group=None, force_exchange: bool = False, max_steps=None,
+                 gradient_clip_val=None, gradient_clip_algorithm: str = "norm", track_grad_norm: bool = False):
+        """``gradient_clip_val`` / ``gradient_clip_algorithm``: ``pl.Trainer``'s two gradient options, which the reference passes
+        through ``trainer_params``: ``"norm"`` = ``clip_grad_norm_(params, val)``, ``"value"`` = ``clip_grad_value_(params, val)``,
+        applied to the mean gradient over the ranks (behind the exchange and its 1 / world_size), so every rank clips alike.  None
+        or 0: no clipping.  Fused optimizer: decided on the device inside the optimizer launch (optim.py), no host synchronisation;
+        ``p.grad`` keeps the unclipped sum.  Otherwise torch's functions on the optimizer's parameters.
+        ``track_grad_norm``: form the total gradient norm without clipping.  Whenever the norm is formed (``"norm"`` clipping or
+        tracking) ``last_grad_norm`` holds it after ``train_step``: the norm of the mean gradient BEFORE clipping, identical on every
+        rank; a device fp32 scalar on the fused path (read it when you log: reading synchronises), torch's returned norm otherwise.
+        The range guard keeps its meaning: a step whose flag is raised is dropped whole, clipped or not, and its ``last_grad_norm``
+        may be inf.
+        ``max_steps``: length of the run for modules whose training step depends on its progress (the consistency model's iCT
         schedule, which under Lightning reads ``trainer.max_steps`` / ``global_step``): when given, ``module._dp_progress =
         (steps done so far, max_steps)`` is set before every ``step_and_backward``.  None: nothing is published.
         ``force_exchange``: issue the collectives with ONE rank too (a sum over one rank is the identity: the self-test of the
@@ -101,6 +112,14 @@ class DataParallelTrainer:
         self.ema_decay = ema_decay
         self.max_steps = max_steps
         self.steps_done = 0
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm={gradient_clip_algorithm!r}: expected 'norm' or 'value'")
+        if gradient_clip_val is not None and not gradient_clip_val >= 0:
+            raise ValueError(f"gradient_clip_val must be None or >= 0, got {gradient_clip_val!r}")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.track_grad_norm = bool(track_grad_norm)
+        self.last_grad_norm = None
         self._ema = None
         # (exact classes: a subclass may change the update)
         if self.fused and type(self.optimizer) not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.RAdam):
@@ -234,12 +253,16 @@ class DataParallelTrainer:
         self.last_skip = skip
         if self.fused:
             # the 1 / world_size of the gradient mean rides in the optimizer launch
-            self.optimizer.step(grad_scale=1.0 / self.world, skip_flag=skip)
+            clip = self._clip_kwargs()
+            self.optimizer.step(grad_scale=1.0 / self.world, skip_flag=skip, **clip)
+            if clip:
+                self.last_grad_norm = self.optimizer.last_grad_norm
         else:
             if self.world > 1:
                 flats = list(flat) if isinstance(flat, (list, tuple)) else [flat]
                 for f in flats:
                     f.mul_(1.0 / self.world)
+            self._clip_unfused()
             self.optimizer.step()
             if self._ema is not None:
                 with torch.no_grad():
@@ -249,6 +272,30 @@ class DataParallelTrainer:
             self.scheduler.step()
         self.steps_done += 1
         return loss
+
+    def _clip_kwargs(self) -> dict:
+        """the clipping / tracking arguments of the fused optimizer's step; empty with the defaults: the same call and the same launches as without these options"""
+        kw = {}
+        if self.gradient_clip_val is not None:
+            kw["max_grad_norm" if self.gradient_clip_algorithm == "norm" else "clip_value"] = self.gradient_clip_val
+        if self.track_grad_norm:
+            kw["track_grad_norm"] = True
+        return kw
+
+    def _clip_unfused(self):
+        """torch's optimizer: torch's clipping functions on the gradients it is about to consume (the mean over the ranks)"""
+        val, norm_alg = self.gradient_clip_val, self.gradient_clip_algorithm == "norm"
+        if val is None and not self.track_grad_norm:
+            return
+        ps = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+        if val is not None and norm_alg:
+            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(ps, val)
+            return
+        if self.track_grad_norm:   # (before the clamp, like the fused path)
+            with torch.no_grad():
+                self.last_grad_norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in ps]))
+        if val is not None:
+            torch.nn.utils.clip_grad_value_(ps, val)
 
     AGREE_EVERY = 64   # steps between the (host-synchronous) checks whether every rank has left the fp16-range scheme
 
