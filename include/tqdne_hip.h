@@ -568,6 +568,16 @@ int tq_radam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double st
                               double rect, double ema_weight, double grad_scale, const int32_t* skip_flag, const float* clip_coef,
                               double clip_value, hipStream_t stream);
 
+/* The second half of the EMA callback (ema.py:30-48: EMA weights into the module before every validation / test / predict pass, the
+ * training weights back afterwards) as an exchange in place, an addition to ABI 8: for every chunk with ema != NULL, p[i] <-> ema[i] for
+ * i < n.  One launch for the whole model, the optimizer kernel's geometry (one workgroup of 256 threads per chunk, 16-byte body, one-word
+ * tail), no second copy of the weights.  Only p, ema and n of a chunk are read (g, m, v may be NULL); chunks whose ema is NULL are left
+ * alone.  Bit patterns are moved, nothing is rounded: NaN payloads, infinities, -0.0 and denormals arrive unchanged, and two calls restore
+ * both sides bit for bit.  The caller invalidates whatever it derived from the parameters (DataParallelTrainer.ema_weights bumps their
+ * autograd versions, so the packed weights follow).
+ * NULL table with n_chunks > 0, or n_chunks < 0: TQ_ERR_ARG; n_chunks == 0: 0, nothing launched. */
+int tq_ema_swap(const TqAdamChunk* chunks, int n_chunks, hipStream_t stream);
+
 /* ---- signal representation either side of the path (representation.py:41-60, MovingAverageEnvelope) ------- */
 /* x (N, C, T) fp32 NCW -> out (N, 2C, T) fp32: channels [0, C) = x / (env + eps), [C, 2C) = log(env + log_eps) - log(log_eps)/2,
  * env = mean of |x| over [t - W/2, t + (W-1)/2] with zeros outside the signal (np.convolve(..., mode="same")); float64 inside,

@@ -197,6 +197,7 @@ _PROTOS = {
     "tq_radam_ema_step_clipped": (I, [VP, I] + [C.c_double] * 7 + [VP, VP, C.c_double, VP]),
     "tq_grad_sumsq": (I, [VP, I, VP, VP]),
     "tq_grad_clip_coef": (I, [VP, I, C.c_double, C.c_double, VP, VP]),
+    "tq_ema_swap": (I, [VP, I, VP]),
     "tq_conv1d_bwd_data": (I, [VP] * 11),
     "tq_conv1d_bwd_weight_workspace": (SZ, [VP]),
     "tq_conv1d_bwd_weight": (I, [VP] * 8 + [SZ, VP]),

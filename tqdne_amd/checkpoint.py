@@ -156,8 +156,9 @@ def load_checkpoint(path, map_location="cpu", extra_safe_globals=()) -> Dict[str
 
 def save_checkpoint(module: torch.nn.Module, path, *, ema_state: Optional[Dict[str, torch.Tensor]] = None,
                     optimizer: Optional[torch.optim.Optimizer] = None, lr_scheduler=None, epoch: int = 0,
-                    global_step: int = 0) -> None:
-    """Write ``module`` in the layout of a Lightning checkpoint of the reference class of the same name."""
+                    global_step: int = 0, extra: Optional[Dict[str, Any]] = None) -> None:
+    """Write ``module`` in the layout of a Lightning checkpoint of the reference class of the same name.  ``extra``: further top-level
+    keys (a reference loader ignores the ones it does not know; DataParallelTrainer.save_checkpoint keeps its own state under one)."""
     ckpt: Dict[str, Any] = OrderedDict()
     ckpt["epoch"] = int(epoch)
     ckpt["global_step"] = int(global_step)
@@ -169,6 +170,10 @@ def save_checkpoint(module: torch.nn.Module, path, *, ema_state: Optional[Dict[s
     ckpt["hyper_parameters"] = dict(getattr(module, "hparams", {}) or {})
     if ema_state is not None:
         ckpt["ema_state"] = OrderedDict((k, v.detach().cpu()) for k, v in ema_state.items())
+    for k, v in (extra or {}).items():
+        if k in ckpt:
+            raise ValueError(f"extra key {k!r} collides with a key of the Lightning layout")
+        ckpt[k] = v
     torch.save(ckpt, path, pickle_module=_RemapPickle)
 
 

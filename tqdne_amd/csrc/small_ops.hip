@@ -1168,6 +1168,29 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __res
         out[1] = coef;
     }
 }
+
+// Exchange of the parameters and their EMA in place (the EMA callback's swap around validation, ema.py:30-48), the optimizer kernel's
+// geometry: one workgroup per chunk, a 16-byte body and a one-word tail.  Words are moved as integers: no value is ever formed, so NaN
+// payloads, infinities, -0.0 and denormals come through bit for bit.  Reads p, ema and n only.
+__global__ __launch_bounds__(256) void ema_swap_kernel(const TqAdamChunk* __restrict__ chunks) {
+    const TqAdamChunk c = chunks[blockIdx.x];
+    if (!c.ema) return;   // (uniform over the workgroup)
+    uint32_t* p = reinterpret_cast<uint32_t*>(c.p);
+    uint32_t* e = reinterpret_cast<uint32_t*>(c.ema);
+    const int n4 = c.n & ~3;
+    for (int i = threadIdx.x * 4; i < n4; i += 256 * 4) {
+        const uint4 a = *reinterpret_cast<const uint4*>(p + i);
+        const uint4 b = *reinterpret_cast<const uint4*>(e + i);
+        *reinterpret_cast<uint4*>(p + i) = b;
+        *reinterpret_cast<uint4*>(e + i) = a;
+    }
+    const int i = n4 + threadIdx.x;
+    if (i < c.n) {
+        const uint32_t a = p[i], b = e[i];
+        p[i] = b;
+        e[i] = a;
+    }
+}
 }  // namespace
 
 extern "C" int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,
@@ -1214,6 +1237,14 @@ extern "C" int tq_radam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks
 extern "C" int tq_grad_sumsq(const TqAdamChunk* chunks, int n_chunks, double* partials, hipStream_t stream) {
     if (!chunks || !partials || n_chunks <= 0) return TQ_ERR_ARG;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, stream, chunks, partials);
+    TQ_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int tq_ema_swap(const TqAdamChunk* chunks, int n_chunks, hipStream_t stream) {
+    if (n_chunks < 0 || (!chunks && n_chunks > 0)) return TQ_ERR_ARG;
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(n_chunks), dim3(256), 0, stream, chunks);
     TQ_CHECK_LAUNCH();
     return 0;
 }

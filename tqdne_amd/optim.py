@@ -6,7 +6,9 @@ Semantics are ``torch.optim.Adam(params, lr)`` as configured by the reference (t
 weight decay) and, when ``ema_decay`` is given, the reference's EMA callback (tqdne/ema.py:24-28: ``ema.lerp_(p, 1 - decay)``
 after every optimizer step).  The class is a ``torch.optim.Optimizer``: LR schedulers drive ``param_groups[0]["lr"]`` and
 ``state_dict()`` / ``load_state_dict()`` speak torch Adam's format, so the ``optimizer_states`` of a reference checkpoint load.
-Moments (and the EMA copy) live in flat fp32 buffers; ``state[p]["exp_avg"]`` etc. are views of them.
+Moments (and the EMA copy) live in flat fp32 buffers; ``state[p]["exp_avg"]`` etc. are views of them.  ``swap_ema()`` exchanges
+the parameters with that EMA copy in place (tq_ema_swap, one launch): the callback's other half, EMA weights for validation and
+sampling (tqdne/ema.py:30-48), without a second copy of the model.
 
 ``FusedRAdamEMA`` is the same for ``torch.optim.RAdam(params, lr)``, the consistency model's optimizer (tqdne/consistency_model.py:
 178-190); flat buffers, chunk table, EMA views, version bump and (de)serialisation are ``_FusedFlatOptimizer``'s, shared by both.
@@ -66,20 +68,65 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
                                  exp_avg_sq=self._v[o:o + n].view_as(p))
         self._table = None
         self._table_key = None
+        self._swap_table = None      # the swap's own table, made by the first ``swap_ema``
+        self._swap_key = None
         self._norm_buf = None        # (fp64 partials per chunk, [norm, coefficient]) of the current table, made on first use
         self.last_grad_norm = None   # device fp32 scalar once a step has formed the norm
 
     # ------------------------------------------------------------------ EMA
+    ema_swapped = False   # True between two ``swap_ema()`` calls: the parameters hold the EMA weights, the EMA buffer the training weights
+
     def ema_state(self) -> "OrderedDict[str, torch.Tensor]":
-        """name -> EMA tensor (views), the dict the reference's EMA callback stores under checkpoint['ema_state']."""
+        """name -> EMA tensor (views), the dict the reference's EMA callback stores under checkpoint['ema_state'].  Always the EMA of
+        the training run: while ``ema_swapped`` the values live in the parameters, so the views are of the parameters (detached) and
+        ``checkpoint.save_checkpoint(..., ema_state=optimizer.ema_state())`` keeps writing the EMA under ``ema_state``."""
         if self._ema is None:
             raise RuntimeError("constructed without ema_decay")
         ps = self.param_groups[0]["params"]
+        if self.ema_swapped:
+            return OrderedDict((n, p.detach()) for n, p in zip(self._names, ps))
         return OrderedDict((n, self._ema[o:o + p.numel()].view_as(p)) for n, p, o in zip(self._names, ps, self._offs))
 
     def load_ema_state(self, ema_state):
+        """(while ``ema_swapped`` this writes the parameters: raw copies, so their versions are bumped like ``swap_ema`` does)"""
         for n, t in self.ema_state().items():
             t.copy_(ema_state[n])
+
+    def _build_swap_table(self):
+        """(p, ema, n) rows over EVERY optimized parameter, g / m / v null: unlike the step's table it does not depend on ``p.grad``
+        (which skips parameters without a gradient and does not exist before the first step)"""
+        ps = self.param_groups[0]["params"]
+        rows = []
+        for p, o in zip(ps, self._offs):
+            n = p.numel()
+            for s in range(0, n, TQ_ADAM_CHUNK):
+                rows.append((p.data_ptr() + 4 * s, self._ema.data_ptr() + 4 * (o + s), min(TQ_ADAM_CHUNK, n - s)))
+        arr = (TqAdamChunk * len(rows))()
+        for i, r in enumerate(rows):
+            arr[i].p, arr[i].ema, arr[i].n = r
+        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        self._swap_table = host.to(self._m.device)
+        self._swap_chunks = len(rows)
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every optimized parameter with its EMA in place: ONE launch (tq_ema_swap) on the current stream, no second copy of
+        the model.  Toggles ``ema_swapped`` and bumps the parameters' autograd versions, as ``step`` does, so that the engines' packed
+        weights follow.  While swapped ``step`` refuses to run (it would update the EMA as if it were the weights); ``ema_state()``
+        keeps meaning the EMA of the run, and ``state_dict()`` is unaffected (moments and step count do not move).  The MODULE's
+        ``state_dict()`` holds the EMA weights while swapped: write checkpoints after swapping back (DataParallelTrainer.save_checkpoint
+        refuses inside ``ema_weights()``)."""
+        if self._ema is None:
+            raise RuntimeError("constructed without ema_decay")
+        ps = self.param_groups[0]["params"]
+        key = tuple(p.data_ptr() for p in ps)
+        if key != self._swap_key:
+            self._build_swap_table()
+            self._swap_key = key
+        stream = torch.cuda.current_stream(self._m.device).cuda_stream
+        check(self._lib.tq_ema_swap(self._swap_table.data_ptr(), self._swap_chunks, stream), "ema swap")
+        torch._C._increment_version(ps)
+        self.ema_swapped = not self.ema_swapped
 
     # ------------------------------------------------------------------ chunk table
     def _build_table(self):
@@ -131,6 +178,9 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         for name, val in (("max_grad_norm", max_grad_norm), ("clip_value", clip_value)):
             if val is not None and not val > 0:
                 raise ValueError(f"{name} must be positive, got {val!r}")
+        if self.ema_swapped:
+            raise RuntimeError("the parameters hold the EMA weights (swap_ema / DataParallelTrainer.ema_weights): a step now would "
+                               "update the EMA as if it were the weights; swap back first")
         loss = closure() if closure is not None else None
         key = self._key()
         if key != self._table_key:
@@ -164,6 +214,13 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         return loss
 
     # ------------------------------------------------------------------ (de)serialisation in torch Adam's format
+    def state_dict(self):
+        """torch's format, with a ``step`` tensor of its own per parameter: the one shared scalar kept here would stay shared through
+        ``torch.save`` / ``deepcopy``, and torch's Adam, loading it, would then count every step once per parameter."""
+        sd = super().state_dict()
+        sd["state"] = {k: dict(st, step=st["step"].clone()) for k, st in sd["state"].items()}
+        return sd
+
     def load_state_dict(self, state_dict):
         ps = self.param_groups[0]["params"]
         st = state_dict["state"]

@@ -46,6 +46,11 @@ def reset_dropout_counter(value: int = 0) -> None:
     _state["counter"] = int(value)
 
 
+def dropout_counter() -> int:
+    """Calls of ``next_dropout_seed`` so far (what a checkpoint keeps so that a resumed run draws the masks the original would have)."""
+    return _state["counter"]
+
+
 def dropout_seed_for(initial_seed: int, rank: int, counter: int) -> int:
     """The seed ``next_dropout_seed`` returns for call number ``counter`` (pure function; the tests rebuild masks from it)."""
     return _mix(_mix((int(initial_seed) & _M64) ^ ((int(rank) + 1) * 0xD1B54A32D192ED03 & _M64)) ^ (int(counter) & _M64))

@@ -10,11 +10,18 @@ input blocks, stem, embedding MLPs) and calls back as each contiguous bucket bec
 issued right there (asynchronously: on RCCL's own stream, ordered behind the launches enqueued so far) and runs under the
 rest of the sweep.  Only the optimizer launch waits for the exchange.  Every rank cuts and issues the buckets identically
 (the cut depends on the model and ``bucket_bytes`` only), so the collectives match up by construction.
+
+The rest of the fit loop: ``ema_weights()`` is the second half of the reference's EMA callback (tqdne/ema.py:30-48: EMA weights into the
+module before every validation / test / predict pass, the training weights back afterwards), ``validate`` / ``evaluate`` run
+``validation_step`` / ``evaluate`` under it, ``save_checkpoint`` / ``load_checkpoint`` write and resume the Lightning layout of
+checkpoint.py, and ``fit`` is the thin loop over all of it with ModelCheckpoint's ``last.ckpt`` + best ``save_top_k`` (training.py:54-65).
 """
 
 from __future__ import annotations
 
+import contextlib
 import inspect
+import os
 
 import torch
 import torch.distributed as dist
@@ -211,6 +218,8 @@ class DataParallelTrainer:
     def train_step(self, batch):
         """loss, backward (HIP) with the gradient exchange riding under it, Adam, cosine LR.  Returns the local loss (a device
         scalar; no host sync here -- the reference's ``loss.item()`` logging, edm.py:138, belongs to the caller)."""
+        if self._ema_active:
+            raise RuntimeError("train_step inside ema_weights(): the module holds the EMA weights; leave the context first")
         works = []
         self.last_bucket_sizes = []
         self.last_tail_words = 0      # words of ours that rode at the end of the last gradient bucket (the range-guard pair: 2)
@@ -364,9 +373,180 @@ class DataParallelTrainer:
             words[1:2].fill_(1.0)
 
     def ema_state(self):
-        """name -> EMA weights, as the reference's EMA callback stores them in a checkpoint (tqdne/ema.py:50-51)."""
+        """name -> EMA weights, as the reference's EMA callback stores them in a checkpoint (tqdne/ema.py:50-51).  Always the EMA of
+        the training run, also inside ``ema_weights()`` (fused path: views of the parameters then, where the swap put the values)."""
         if self.fused:
             return self.optimizer.ema_state()
         if self._ema is None:
             raise RuntimeError("constructed without ema_decay")
         return self._ema
+
+    # ------------------------------------------------------------------ validation / prediction on the EMA weights
+    _ema_active = False   # inside ``ema_weights()``
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The second half of the reference's EMA callback (tqdne/ema.py:30-48): inside the context the module holds the EMA weights,
+        afterwards -- also when the body raises -- the training weights again; parameters and EMA are then bit for bit what they were.
+        Fused optimizer: ``optimizer.swap_ema()`` twice, one small launch each, nothing copied or allocated (tq_ema_swap).  Otherwise
+        ``torch._foreach_copy_`` through one temporary list.  Only the optimized / trainable parameters change (frozen parameters and
+        buffers stay, like the reference's ``load_state_dict(ema_state, strict=False)``); the parameters' versions move, so the packed
+        weights follow.  Not re-entrant; ``train_step``, ``save_checkpoint`` and ``load_checkpoint`` refuse to run inside it."""
+        if self.ema_decay is None:
+            raise RuntimeError("constructed without ema_decay")
+        if self._ema_active:
+            raise RuntimeError("ema_weights() is already active: the module holds the EMA weights (the context does not nest)")
+        saved = None
+        if self.fused:
+            self.optimizer.swap_ema()
+        else:
+            named = dict(self.module.named_parameters())
+            ps = [named[n] for n in self._ema]
+            with torch.no_grad():
+                saved = [p.detach().clone() for p in ps]
+                torch._foreach_copy_(ps, list(self._ema.values()))
+        self._ema_active = True
+        try:
+            yield self.module
+        finally:
+            self._ema_active = False
+            if self.fused:
+                self.optimizer.swap_ema()
+            else:
+                with torch.no_grad():
+                    torch._foreach_copy_(ps, saved)
+
+    @contextlib.contextmanager
+    def _eval_pass(self):
+        """what Lightning sets up around a validation / predict pass: EMA weights when the trainer keeps an EMA, ``module.eval()``,
+        ``torch.no_grad()``; every submodule's mode is put back afterwards (a frozen autoencoder stays in eval mode)"""
+        modes = [(m, m.training) for m in self.module.modules()]
+        weights = self.ema_weights() if self.ema_decay is not None else contextlib.nullcontext()
+        try:
+            with weights, torch.no_grad():
+                self.module.eval()
+                yield
+        finally:
+            for m, mode in modes:
+                m.training = mode
+
+    def validate(self, batches, limit_batches=None):
+        """One validation pass (Lightning's validation loop + the EMA callback): ``module.validation_step(batch, i)`` for every batch
+        (the first ``limit_batches`` if given) on the EMA weights when the trainer keeps an EMA, in eval mode, without gradients.
+        Returns sum(loss_i * B_i) / sum(B_i) with B_i = batch["signal"].shape[0] as a device scalar; with several ranks both sums go
+        over the ranks in ONE collective of two words -- for equally sized batches Lightning's ``sync_dist=True`` epoch mean, the value
+        the reference's ModelCheckpoint monitors (training.py:54-65).  Every rank returns the same value."""
+        dev = next(self.module.parameters()).device
+        acc = torch.zeros(2, dtype=torch.float64, device=dev)   # [sum of loss * B, sum of B]
+        with self._eval_pass():
+            for i, batch in enumerate(batches):
+                if limit_batches is not None and i >= limit_batches:
+                    break
+                if self.max_steps is not None:
+                    self.module._dp_progress = (self.steps_done, self.max_steps)
+                loss = self.module.validation_step(batch, i)
+                B = batch["signal"].shape[0]
+                acc[0] += loss.detach().to(torch.float64) * B
+                acc[1] += B
+        if self.world > 1:
+            self._allreduce_async(acc).wait()
+        return (acc[0] / acc[1]).float()
+
+    def evaluate(self, batch):
+        """``module.evaluate(batch)`` -- the samples the reference's predict loop and LogCallback draw -- under the conditions of
+        ``validate``: EMA weights when there are any, eval mode, no gradients."""
+        with self._eval_pass():
+            return self.module.evaluate(batch)
+
+    # ------------------------------------------------------------------ checkpoints, resuming
+    EXTRA_KEY = "tqdne_amd_trainer"   # our one top-level key in a checkpoint; a reference loader ignores it
+
+    def save_checkpoint(self, path, epoch: int = 0):
+        """``checkpoint.save_checkpoint`` (the Lightning layout: a reference loader reads it) of the module, the EMA, the optimizer in
+        torch's format, the scheduler and ``global_step = steps_done``, plus what only this trainer needs to continue exactly where it
+        stopped, under ``EXTRA_KEY``: the dropout call counter, the conv scheme of the module's 1-D network and ``steps_done``."""
+        if self._ema_active:
+            raise RuntimeError("save_checkpoint inside ema_weights(): the module holds the EMA weights; leave the context first")
+        from . import rng
+        from .checkpoint import save_checkpoint
+        net = self._network()
+        extra = {self.EXTRA_KEY: {"dropout_counter": rng.dropout_counter(), "steps_done": self.steps_done,
+                                  "conv_scheme": None if net is None else getattr(net, "_conv_scheme", "auto")}}
+        save_checkpoint(self.module, path, ema_state=self.ema_state() if self.ema_decay is not None else None,
+                        optimizer=self.optimizer, lr_scheduler=self.scheduler, epoch=epoch, global_step=self.steps_done, extra=extra)
+
+    def load_checkpoint(self, path):
+        """Put module, optimizer, EMA, scheduler and step count back where ``save_checkpoint`` -- or the reference's ModelCheckpoint --
+        left them (``trainer.fit(..., ckpt_path=...)``).  The weights are copied in place, so the parameters' versions move and the
+        packed weights follow.  A checkpoint without ``ema_state`` starts the EMA from the loaded weights (the callback's
+        ``on_fit_start``); one without our key (written by the reference) continues at ``steps_done = global_step``.  Returns the
+        checkpoint dict."""
+        if self._ema_active:
+            raise RuntimeError("load_checkpoint inside ema_weights(): leave the context first")
+        from . import rng
+        from .checkpoint import load_checkpoint
+        ckpt = load_checkpoint(path, map_location="cpu")
+        self.module.load_state_dict(ckpt["state_dict"])
+        if ckpt.get("optimizer_states"):
+            self.optimizer.load_state_dict(ckpt["optimizer_states"][0])
+        if self.ema_decay is not None:
+            with torch.no_grad():
+                src = ckpt.get("ema_state") or dict(self.module.named_parameters())
+                if self.fused:
+                    self.optimizer.load_ema_state(src)
+                else:
+                    for n, t in self._ema.items():
+                        t.copy_(src[n])
+        if self.scheduler is not None and ckpt.get("lr_schedulers"):
+            self.scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+        ours = ckpt.get(self.EXTRA_KEY) or {}
+        self.steps_done = int(ours.get("steps_done", ckpt.get("global_step", 0)))
+        if "dropout_counter" in ours:
+            rng.reset_dropout_counter(ours["dropout_counter"])
+        net = self._network()
+        if net is not None and ours.get("conv_scheme") == "bf16x3" and getattr(net, "_conv_scheme", "auto") == "auto":
+            net._conv_scheme = "bf16x3"   # (the run had left the fp16-range scheme: plans built from now on start there ...)
+            for eng in net._engine_cache.values():   # (... and the ones that exist move)
+                if eng.scheme == "auto":
+                    eng._set_scheme_bf16x3()
+        return ckpt
+
+    def fit(self, train_batches, val_batches=None, *, max_steps, val_check_interval=None, limit_val_batches=None, dirpath=None,
+            save_top_k: int = 3, ckpt_path=None):
+        """The loop ``pl.Trainer.fit`` runs for the reference (experiments/train_1d_edm.py; no logger, no callbacks): resume from
+        ``ckpt_path`` if given, then ``train_step`` over ``train_batches`` (a re-iterable of this rank's batches, gone through as many
+        times as it takes) until ``steps_done == max_steps``.  Every ``val_check_interval`` steps: ``validate(val_batches,
+        limit_val_batches)`` and, with ``dirpath``, rank 0 writes ``last.ckpt`` and keeps the ``save_top_k`` checkpoints of lowest
+        validation loss (ModelCheckpoint(monitor="validation/loss", mode="min", save_top_k=3, save_last=True), training.py:54-65),
+        deleting the ones that drop out.  The host reads the validation loss there and nowhere else.  Returns the validation losses
+        as [(steps_done, loss), ...]."""
+        if ckpt_path is not None:
+            self.load_checkpoint(ckpt_path)
+        writer = dirpath is not None and (self.world <= 1 or dist.get_rank(self.group) == 0)
+        if writer:
+            os.makedirs(dirpath, exist_ok=True)
+        kept, history, epoch = [], [], 0   # kept: (loss, path) of the top-k files, best first
+        it = iter(train_batches)
+        while self.steps_done < max_steps:
+            try:
+                batch = next(it)
+            except StopIteration:
+                epoch += 1
+                it = iter(train_batches)
+                batch = next(it)
+            self.train_step(batch)
+            if not val_check_interval or self.steps_done % val_check_interval:
+                continue
+            val = float(self.validate(val_batches, limit_val_batches)) if val_batches is not None else None
+            history.append((self.steps_done, val))
+            if not writer:
+                continue
+            self.save_checkpoint(os.path.join(dirpath, "last.ckpt"), epoch=epoch)
+            if val is not None and save_top_k > 0 and (len(kept) < save_top_k or val < kept[-1][0]):
+                path = os.path.join(dirpath, f"step={self.steps_done}-val_loss={val:.2e}.ckpt")
+                self.save_checkpoint(path, epoch=epoch)
+                kept = sorted(kept + [(val, path)], key=lambda lp: lp[0])
+                for _, old in kept[save_top_k:]:
+                    os.remove(old)
+                kept = kept[:save_top_k]
+        return history
