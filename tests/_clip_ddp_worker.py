@@ -12,30 +12,17 @@ the spread (the norms agreed to 6e-7).  With fewer GPUs than ranks the ranks sha
 exchange goes over gloo, which the trainer stages through host memory."""
 
 import json
-import os
-import sys
 
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _ddp_launch import gather, init_rank
 
 CLIP = 0.05   # below the gradient norm of both steps (asserted by the test from the norms reported here)
 
 
 def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("TQ_TEST_BACKEND", "gloo")
-    ngpu = torch.cuda.device_count()
-    dev = torch.device("cuda", rank % max(ngpu, 1))
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        from tqdne_amd.trainer import init_process_group   # (side streams first, then the communicator)
-        init_process_group("nccl", device=dev, rank=rank, world_size=world, device_id=dev)
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, dev, backend = init_rank()
 
     from conftest import cfg_of, load_golden, rel_err
     from tqdne_amd import LightningEDM, rng
@@ -62,13 +49,6 @@ def main():
         m = InjectedEDM(cfg, {"learning_rate": 1e-4, "max_steps": 10, "eta_min": 0.0})
         m.unet.load_state_dict(sd)
         return m.to(dev).train()
-
-    def gather(t):
-        """``t`` of every rank, as CPU tensors"""
-        t = t.to(dev) if backend == "nccl" else t.cpu()
-        out = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(out, t)
-        return [o.cpu() for o in out]
 
     def train(m, tr, local):
         norms = []

@@ -8,28 +8,15 @@ switch to the rectified update at t = 6, and across the growth of the iCT schedu
 With fewer GPUs than ranks the ranks share cuda:0 and the exchange goes over gloo, which the trainer stages through host memory."""
 
 import json
-import os
-import sys
 
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _ddp_launch import gather, init_rank
 
 
 def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("TQ_TEST_BACKEND", "gloo")
-    ngpu = torch.cuda.device_count()
-    dev = torch.device("cuda", rank % max(ngpu, 1))
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        from tqdne_amd.trainer import init_process_group   # (side streams first, then the communicator)
-        init_process_group("nccl", device=dev, rank=rank, world_size=world, device_id=dev)
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, dev, backend = init_rank()
 
     from conftest import cfg_of, load_golden, rel_err
     from tqdne_amd import UNetModel, rng
@@ -54,13 +41,6 @@ def main():
         net = UNetModel(**cfg)
         net.load_state_dict(sd)
         return LithningConsistencyModel(net, initial_timesteps=10, final_timesteps=40, lr=1e-3).to(dev).train()
-
-    def gather(t):
-        """``t`` of every rank, as CPU tensors"""
-        t = t.to(dev) if backend == "nccl" else t.cpu()
-        out = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(out, t)
-        return [o.cpu() for o in out]
 
     rng.seed_rank(0, rank)
     res = {}

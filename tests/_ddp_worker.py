@@ -8,15 +8,11 @@ host memory by the test's trainer subclass (the product path is RCCL: backend "n
 
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _ddp_launch import init_rank
 
 
 class _Done:
@@ -25,16 +21,7 @@ class _Done:
 
 
 def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("TQ_TEST_BACKEND", "gloo")
-    ngpu = torch.cuda.device_count()
-    dev = torch.device("cuda", rank % max(ngpu, 1))
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        from tqdne_amd.trainer import init_process_group   # (side streams first, then the communicator)
-        init_process_group("nccl", device=dev, rank=rank, world_size=world, device_id=dev)
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, dev, backend = init_rank()
 
     from conftest import cfg_of, load_golden, rel_err
     from tqdne_amd import LightningEDM, rng

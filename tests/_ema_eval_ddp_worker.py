@@ -9,28 +9,15 @@ the ranks inside and after ``ema_weights()``.  With fewer GPUs than ranks the ra
 the trainer stages through host memory."""
 
 import json
-import os
-import sys
 
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _ddp_launch import gather, init_rank
 
 
 def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("TQ_TEST_BACKEND", "gloo")
-    ngpu = torch.cuda.device_count()
-    dev = torch.device("cuda", rank % max(ngpu, 1))
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        from tqdne_amd.trainer import init_process_group   # (side streams first, then the communicator)
-        init_process_group("nccl", device=dev, rank=rank, world_size=world, device_id=dev)
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, dev, backend = init_rank()
 
     from conftest import cfg_of, load_golden
     from tqdne_amd import LightningEDM, rng
@@ -47,13 +34,6 @@ def main():
     def batch_of(B, seed):
         g = torch.Generator().manual_seed(seed)
         return {"signal": (0.5 * torch.randn(B, 3, 256, generator=g)).to(dev), "cond": torch.randn(B, 5, generator=g).to(dev)}
-
-    def gather(t):
-        """``t`` of every rank, as CPU tensors"""
-        t = t.to(dev) if backend == "nccl" else t.cpu()
-        out = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(out, t)
-        return [o.cpu() for o in out]
 
     def same_on_all_ranks(t):
         ts = gather(t)

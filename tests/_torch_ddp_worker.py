@@ -9,15 +9,11 @@ gradients at once from the HIP backward plan -- this worker checks that the redu
 one-rank run's.  With fewer GPUs than ranks the ranks share cuda:0 and the process group is gloo (CUDA tensors staged by gloo)."""
 
 import json
-import os
-import sys
 
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _ddp_launch import init_rank
 
 
 def redirected_step(ddp, module, *args, **kw):
@@ -38,16 +34,7 @@ def redirected_step(ddp, module, *args, **kw):
 
 
 def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("TQ_TEST_BACKEND", "gloo")
-    ngpu = torch.cuda.device_count()
-    dev = torch.device("cuda", rank % max(ngpu, 1))
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        from tqdne_amd.trainer import init_process_group
-        init_process_group("nccl", device=dev, rank=rank, world_size=world, device_id=dev)
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, dev, backend = init_rank()
 
     from conftest import cfg_of, load_golden, rel_err
     from tqdne_amd import LightningEDM, rng

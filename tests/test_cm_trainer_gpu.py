@@ -3,16 +3,13 @@ reference's own step (micro_cm_step.npz) and against ``step()`` + ``backward()``
 DataParallelTrainer with the one-launch RAdam + EMA against torch.optim.RAdam applied to the trainer's own gradients, the iCT schedule
 fed by ``max_steps=``; the range guard; two ranks."""
 
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from _ddp_launch import run_ranks
 from conftest import GOLDEN, ROOT, cfg_of, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -22,14 +19,6 @@ TOL = 1e-3   # tests/test_hip_unet.py's bar for test_consistency_training_step_v
 
 def dev():
     return torch.device("cuda:0")
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _model(dropout=None, **kw):
@@ -235,29 +224,7 @@ def test_raised_range_flag_drops_the_step_on_the_device():
 def test_two_rank_consistency_training():
     """two ranks on a global batch of 4 x 3 x 256 (tests/_cm_ddp_worker.py): the reduced gradients are the one-rank full-batch gradients
     (tests/test_ddp_gpu.py's bars), and after 7 fused RAdam steps the replicas are bit-equal"""
-    world = 2
-    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), TQ_TEST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_cm_ddp_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=400)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-4000:]}"
-    line = [l for l in outs[0].splitlines() if l.startswith("DDP_RESULT ")][-1]
-    res = json.loads(line[len("DDP_RESULT "):])
-    print(backend, res)
+    res = run_ranks("_cm_ddp_worker.py", timeout=400)
     for mode in ("overlap", "after"):
         r = res[mode]
         assert r["err_flat"] < 1e-5 and r["err_worst_tensor"] < 5e-4, (mode, r)  # (B = 2 and B = 4 plans round differently)

@@ -3,26 +3,13 @@ give the one-rank full-batch gradients, with the exchange overlapped with the ba
 Two ranks: RCCL ("nccl") when the box has >= 2 GPUs, otherwise both ranks share cuda:0 and exchange over gloo (host staged by
 the test worker).  Also: the backward plan's bucket callbacks tile the gradient buffer and fire only once a bucket is final."""
 
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 import torch
 
-from conftest import ROOT, cfg_of, load_golden, rel_err
+from _ddp_launch import run_ranks
+from conftest import cfg_of, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.timeout(900)
@@ -30,29 +17,7 @@ def _free_port():
 def test_two_rank_gradients_equal_full_batch_gradients(which):
     """``paper``: BASELINE cfg2's model (the paper UNet under data parallelism; 16 MB buckets = the trainer's default: four of them leave
     from inside the sweep) on a global batch of 4 x 3 x 512 over two ranks"""
-    world = 2
-    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), TQ_TEST_BACKEND=backend, TQ_TEST_CONFIG=which, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_ddp_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=500)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-4000:]}"
-    line = [l for l in outs[0].splitlines() if l.startswith("DDP_RESULT ")][-1]
-    res = json.loads(line[len("DDP_RESULT "):])
-    print(backend, res)
+    res = run_ranks("_ddp_worker.py", 2, {"TQ_TEST_CONFIG": which}, timeout=500)
     for mode in ("overlap", "after"):
         r = res[mode]
         assert r["err_flat"] < 1e-5 and r["err_worst_tensor"] < 5e-4, (mode, r)  # (B = 4 and B = 8 plans round differently)

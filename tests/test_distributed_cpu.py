@@ -2,20 +2,13 @@
 The data path itself has no collective (independent waveforms); the only exchange is the gradient all-reduce."""
 
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _ddp_launch import free_port as _free_port
 
 
 def _worker(rank, world, port, ret):

@@ -11,15 +11,12 @@ steps differ in the last bits (the backward's GroupNorm-affine atomics), so the 
 ``test_fused_and_torch_adam_train_the_same_trajectory``'s bars: losses rel 2e-4, at least 90 % of the tensors within 2e-3, two named
 conv weights within 2e-3 (the autoencoder has no tensors of those names: its first and last conv stand in)."""
 
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from _ddp_launch import run_ranks
 from conftest import ROOT, cfg_of, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -430,6 +427,61 @@ def test_a_resumed_run_continues_the_run_it_was_saved_from(which, tmp_path):
         assert torch.equal(tr_c.ema_state()[n].cpu(), t), n
 
 
+def test_a_run_that_left_the_fp16_range_scheme_resumes_on_bf16x3(tmp_path):
+    """The range guard fires in the middle of a run (raised the way the range-guard test of tests/test_trainer_gpu.py raises it: a
+    residual stream is blown up); the checkpoint written afterwards records the scheme.  A fresh trainer that already holds a plan on
+    the fp16-range scheme must come out of ``load_checkpoint`` with model, existing plans and later plans on bf16x3, and its next step
+    must be the saved run's next step (the bar of test_a_resumed_run_continues_the_run_it_was_saved_from)."""
+    import warnings
+
+    from tqdne_amd import rng
+    from tqdne_amd.trainer import DataParallelTrainer
+    a, tr_a, batch = _trained("edm", steps=2)
+    assert a.unet._conv_scheme == "auto" and all(e.scheme == "auto" for e in a.unet._engine_cache.values())
+    with torch.no_grad():   # blow up the residual stream behind the first ResBlock
+        for n, p in a.unet.named_parameters():
+            if n.startswith("input_blocks.1.0.out_layers.3."):
+                p.mul_(3.0e5)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # ("activations approach the fp16 range")
+        for k in range(6):   # the first of these steps raises the flag; the host sees it at the start of one of the next forwards
+            if a.unet._conv_scheme == "bf16x3":
+                break
+            torch.manual_seed(200 + k)
+            tr_a.train_step(batch)
+            torch.cuda.synchronize()
+    assert a.unet._conv_scheme == "bf16x3" and all(e.scheme == "bf16x3" for e in a.unet._engine_cache.values())
+    path = str(tmp_path / "bf16x3.ckpt")
+    tr_a.save_checkpoint(path)
+    counter = rng.dropout_counter()
+
+    b, tkw = MAKE["edm"]()
+    tr_b = DataParallelTrainer(b, world_size=1, ema_decay=EMA, **tkw)
+    _infer("edm", b, batch)
+    plans = list(b.unet._engine_cache.values())
+    assert plans and all(e.scheme == "auto" for e in plans) and b.unet._conv_scheme == "auto"
+    tr_b.load_checkpoint(path)
+    assert b.unet._conv_scheme == "bf16x3"
+    assert list(b.unet._engine_cache.values()) == plans and all(e.scheme == "bf16x3" for e in plans)
+    assert b.unet._engine(3, 256, dev()).scheme == "bf16x3"   # a plan built afterwards starts there
+    _assert_same_state("edm", a, tr_a, b, tr_b)
+
+    losses = []
+    for tr in (tr_b, tr_a):
+        rng.reset_dropout_counter(counter)
+        torch.manual_seed(1000)
+        losses.append(float(tr.train_step(batch)))
+    print("loss resumed", losses[0], "original", losses[1])
+    assert losses[0] == pytest.approx(losses[1], rel=2e-4)
+    w_a, w_b = _weights(a), _weights(b)
+    errs = {k: rel_err(w_b[k], w_a[k], elem=False) for k in w_a if w_a[k].is_floating_point()}
+    close = sum(e < 2e-3 for e in errs.values())
+    print("weights within 2e-3:", close, "of", len(errs), "; worst", max(errs.items(), key=lambda kv: kv[1]))
+    assert close >= 0.9 * len(errs)
+    assert all(errs[n] < 2e-3 for n in NAMED["edm"])
+    assert tr_a.steps_done == tr_b.steps_done == tr_b.optimizer._step
+
+
 def test_fit_validates_keeps_the_best_checkpoints_and_resumes(tmp_path):
     from tqdne_amd.trainer import DataParallelTrainer
     train = [_batch("edm", 2, seed=40 + i) for i in range(2)]
@@ -454,41 +506,11 @@ def test_fit_validates_keeps_the_best_checkpoints_and_resumes(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ two ranks
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 @pytest.mark.timeout(600)
 def test_two_ranks_validate_to_the_same_value_on_equal_ema_weights():
     """tests/_ema_eval_ddp_worker.py: two ranks train two steps of the micro EDM model on halves of a global batch, then validate on
     different batches: the same value on both ranks, equal parameters inside and after the context"""
-    world = 2
-    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), TQ_TEST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_ema_eval_ddp_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=400)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-4000:]}"
-    line = [l for l in outs[0].splitlines() if l.startswith("DDP_RESULT ")][-1]
-    res = json.loads(line[len("DDP_RESULT "):])
-    print(backend, res)
+    res = run_ranks("_ema_eval_ddp_worker.py", timeout=400)
     assert res["values_equal"] and res["value"] > 0 and res["value"] == pytest.approx(res["by_hand"], rel=1e-6), res
     assert res["inside_equal"] and res["after_equal"] and res["inside_is_ema"] and res["restored"], res
     assert res["ema_differs"] and res["steps"] == 2, res

@@ -7,15 +7,12 @@ these shapes and by 6e-4 on one 15.6 M-element tensor; the kernel's fp64 partial
 rounded to fp32, multiplied into the fp32 gradients, and torch.optim.Adam / AdamW / RAdam + ``_foreach_lerp_`` run on the CPU as in
 tests/test_radam_gpu.py.  Bar: 1e-6 relative, that file's and tests/test_optim.py's."""
 
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from _ddp_launch import run_ranks
 from conftest import ROOT, cfg_of, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -337,42 +334,12 @@ def test_trainer_defaults_form_no_norm():
 
 
 # ------------------------------------------------------------------------------------------------ trainer, two ranks
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 @pytest.mark.timeout(600)
 def test_two_rank_clipped_training_reproduces_the_full_batch_run():
     """tests/_clip_ddp_worker.py: two ranks on halves of a fixed global batch of the micro EDM model, gradient_clip_val on, against one
     rank on the full batch: ``last_grad_norm`` of both steps and the parameters after two steps, at tests/test_ddp_gpu.py's bars for the
     unclipped gradients (1e-5 over the flat vector, 5e-4 for the worst tensor against its own scale)."""
-    world = 2
-    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), TQ_TEST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_clip_ddp_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=400)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-4000:]}"
-    line = [l for l in outs[0].splitlines() if l.startswith("DDP_RESULT ")][-1]
-    res = json.loads(line[len("DDP_RESULT "):])
-    print(backend, res)
+    res = run_ranks("_clip_ddp_worker.py", timeout=400)
     assert all(n > res["clip"] for n in res["norms_full"]), "both steps must have been clipped"
     for a, b in zip(res["norms"], res["norms_full"]):
         assert abs(a - b) < 1e-5 * b, res

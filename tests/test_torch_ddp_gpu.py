@@ -4,45 +4,16 @@ both on cuda:0 over gloo) wrap ``tqdne_amd.LightningEDM`` in torch's DDP -- defa
 ``static_graph=True`` (Lightning's defaults differ by version) and many small buckets -- and must reproduce the one-rank full-batch
 gradients and Adam steps.  The worker is tests/_torch_ddp_worker.py."""
 
-import json
-import os
-import subprocess
-import sys
-
 import pytest
-import torch
 
-from conftest import ROOT
-from test_ddp_gpu import _free_port
+from _ddp_launch import run_ranks
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.timeout(900)
 def test_torch_ddp_wrapper_reproduces_full_batch_gradients_and_steps():
-    world = 2
-    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), TQ_TEST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_torch_ddp_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=800)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-6000:]}"
-    line = [l for l in outs[0].splitlines() if l.startswith("TORCH_DDP_RESULT ")][-1]
-    res = json.loads(line[len("TORCH_DDP_RESULT "):])
-    print(backend, json.dumps(res, indent=1))
+    res = run_ranks("_torch_ddp_worker.py", timeout=800, tag="TORCH_DDP_RESULT")
     assert set(res) == {"default", "bucket_view", "static_graph", "small_buckets"}
     for mode, r in res.items():
         # (the B = 4 per-rank plan and the B = 8 one-rank plan associate the GroupNorm / weight-gradient sums differently: 1e-5 on

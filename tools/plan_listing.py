@@ -5,6 +5,7 @@ must leave every launch, argument and order as it was).
     python tools/plan_listing.py --diff OLD.txt NEW.txt             TQDNE_HIP_LIB=<path to libtqdne_hip.so>; then compare the two files)
     python tools/plan_listing.py --equal OLD.pt NEW.pt             (the inference outputs of every case, torch.equal)
     python tools/plan_listing.py --models LISTING.txt [OUTPUTS.pt] (the layer ABOVE the plans, see below; same --diff / --equal)
+    python tools/plan_listing.py --trainer LISTING.txt [OUTPUTS.pt] (the training layer, see below; same --diff / --equal)
 
 ``--diff`` is a line diff that lets ONE kind of line move within its run: the transposed pack of an input layer's weights for the input
 gradient (tq_pack_conv_weight mode 1), which only has to precede that gradient's launch: such lines are compared at the end of the run
@@ -23,7 +24,14 @@ per call every library launch in order, with its stream (numbered by first appea
 against everything the modules, their scratch caches, their plans and the inputs hold.  A device address that resolves to nothing held
 (a temporary of the call) is "tmp<k>", k by first appearance within the call.  torch.manual_seed(0) and rng.seed_rank(0) precede every
 case.  In OUTPUTS.pt the inference outputs and samples carry plain names (``--equal`` demands torch.equal); losses and gradients, which
-pass through the gradient kernels' atomics, carry a leading "~" (``--equal`` reports how many differ and the largest difference)."""
+pass through the gradient kernels' atomics, carry a leading "~" (``--equal`` reports how many differ and the largest difference).
+
+``--trainer`` lists what the training layer (trainer.py, optim.py) makes of ``DataParallelTrainer``'s public calls, per case and per call:
+every library launch in order with its stream and resolved arguments, every ``torch.distributed`` collective the trainer issues (kind,
+dtype, elements, asynchronous or not) where it was issued between them, and after each call the decoded rows of the fused optimizer's
+step table and swap table.  In OUTPUTS.pt those tables (buffer number and offset per address) and everything of the two bare-optimizer
+cases -- fixed synthetic gradients, no atomics -- carry plain names; losses, trained parameters and the norms of real backward passes
+carry the "~"."""
 
 import ctypes as C
 import difflib
@@ -454,6 +462,227 @@ def model_listing(out, outputs):
                 outputs[f"{'~' if k[0] == '~' else ''}{title} / {tag} / {k.lstrip('~')}"] = v.detach().clone().cpu()
 
 
+class Collectives:
+    """``dist.all_reduce`` / ``dist.broadcast`` wrapped for the duration: while the recorder logs, each call leaves ("@kind", [dtype,
+    elements, async?]) in its log, between the launches it was issued between."""
+
+    def __init__(self, rec):
+        self.rec = rec
+
+    def __enter__(self):
+        import torch.distributed as dist
+        self.saved = {k: getattr(dist, k) for k in ("all_reduce", "broadcast")}
+        for kind, real in self.saved.items():
+            def f(t, *a, _kind=kind, _real=real, **k):
+                if self.rec.log is not None:
+                    self.rec.log.append(("@" + _kind, [str(t.dtype), t.numel(), bool(k.get("async_op", False))]))
+                return _real(t, *a, **k)
+            setattr(dist, kind, f)
+
+    def __exit__(self, *exc):
+        import torch.distributed as dist
+        for kind, real in self.saved.items():
+            setattr(dist, kind, real)
+
+
+def trainer_cases():
+    """(title, build() -> (roots, optimizers, [(tag, call() -> {name: tensor to save})])): ``roots`` is what the addresses are resolved
+    against (trainers, modules, inputs), ``optimizers`` the fused optimizers whose step and swap tables are written after every call;
+    a call may append to both.  Only names both sides of a refactor of the training layer have."""
+    import tempfile
+
+    from tqdne_amd import LightningAutoencoder, LightningEDM, LithningConsistencyModel, UNetModel, tiny_1d_unet_config
+    from tqdne_amd.optim import FusedAdamEMA, FusedRAdamEMA
+    from tqdne_amd.trainer import DataParallelTrainer
+    tiny = tiny_1d_unet_config()
+    micro = dict(in_channels=3, out_channels=3, model_channels=32, channel_mult=(1, 2), num_res_blocks=1, attention_resolutions=(2,),
+                 num_heads=4, conv_kernel_size=5, dims=1, cond_features=5, dropout=0.1)
+    coder = dict(model_channels=32, num_res_blocks=1, attention_resolutions=(), channel_mult=(1, 2), conv_kernel_size=3, dims=1, dropout=0.1)
+    opt = {"learning_rate": 1e-3, "max_steps": 10, "eta_min": 0.0}
+    B, T = 2, 256
+
+    def module(kind, cfg=micro):
+        if kind == "edm":
+            return perturbed(LightningEDM(cfg, opt, num_sampling_steps=3), 1).train()
+        if kind == "cm":
+            return perturbed(LithningConsistencyModel(UNetModel(**cfg), initial_timesteps=10, final_timesteps=40), 1).train()
+        return perturbed(LightningAutoencoder(dict(coder, in_channels=3, out_channels=32), dict(coder, in_channels=16, out_channels=3), opt), 1).train()
+
+    def batch(seed=2, cond=True):
+        return dict({"signal": 0.5 * rnd(seed, B, 3, T)}, **({"cond": rnd(seed + 100, B, 5)} if cond else {}))
+
+    def flat(m):
+        return torch.cat([p.detach().flatten() for p in m.parameters()])
+
+    def steps(tr, b, n=3, parameters=True):
+        def step():
+            res = {"~loss": tr.train_step(b).detach()}
+            if tr.last_grad_norm is not None:
+                res["~grad norm"] = tr.last_grad_norm.detach().clone()
+            return res
+        return [(f"train_step {i + 1}", step) for i in range(n)] + [("parameters", lambda: {"~parameters": flat(tr.module)})][:parameters]
+
+    def train(kind, cfg=micro, **kw):
+        def build():
+            m, b = module(kind, cfg), batch(cond=kind != "ae" and bool(cfg["cond_features"]))
+            tr = DataParallelTrainer(m, world_size=1, **kw)
+            return [tr, b], [tr.optimizer] if tr.fused else [], steps(tr, b, parameters=cfg is not tiny)   # (3.5 M of them)
+        return build
+
+    def evaluate():
+        def build():
+            m, b = module("edm"), batch()
+            tr = DataParallelTrainer(m, world_size=1, ema_decay=0.9)
+            x, sigma = rnd(12, B, 3, T), rnd(13, B).abs() + 0.1
+
+            def forward():
+                with tr.ema_weights(), torch.no_grad():
+                    return {"~y on the EMA weights": m(x, sigma, None, b["cond"])}
+            return [tr, b, x, sigma], [tr.optimizer], steps(tr, b, 1)[:1] + [
+                ("validate on two batches", lambda: {"~validation loss": tr.validate([batch(10), batch(11)])}),
+                ("inference forward inside ema_weights()", forward)]
+        return build
+
+    def resume():
+        def build():
+            m, b = module("edm"), batch()
+            tr = DataParallelTrainer(m, world_size=1, ema_decay=0.9)
+            path = os.path.join(tempfile.mkdtemp(), "listing.ckpt")
+            roots, opts = [tr, b], [tr.optimizer]
+            tr2 = []
+
+            def load():
+                tr2.append(DataParallelTrainer(module("edm"), world_size=1, ema_decay=0.9))
+                roots.append(tr2[0])
+                opts.append(tr2[0].optimizer)
+                tr2[0].load_checkpoint(path)
+                return {}
+            return roots, opts, steps(tr, b, 1)[:1] + [
+                ("save_checkpoint", lambda: tr.save_checkpoint(path) or {}), ("load_checkpoint into a fresh trainer", load),
+                ("train_step 2 of the fresh trainer", lambda: {"~loss": tr2[0].train_step(b).detach()}),
+                ("parameters", lambda: {"~parameters": flat(tr2[0].module)})]
+        return build
+
+    def bare(cls, **kw):
+        """the optimizer alone on fixed synthetic gradients: no atomics anywhere, every saved tensor is compared with torch.equal"""
+        def build():
+            sizes = [1, 3, 4, 5, 4095, 4096, 4097, 2 * 4096 + 3, 7]
+            ps = [torch.nn.Parameter(rnd(40 + i, n)) for i, n in enumerate(sizes)]
+            o = cls([(f"p{i}", p) for i, p in enumerate(ps)], lr=1e-3, ema_decay=0.9, **kw)
+            for i, p in enumerate(ps[:-1]):   # (the last parameter never has a gradient: the step's table leaves it out)
+                p.grad = rnd(60 + i, *p.shape)
+
+            def state():
+                return {"parameters": torch.cat([p.detach().flatten() for p in ps]), "m": o._m.clone(), "v": o._v.clone(), "ema": o._ema.clone()}
+
+            def step(**skw):
+                def call():
+                    o.step(**skw)
+                    return dict(state(), **({"grad norm": o.last_grad_norm.clone()} if skw.get("max_grad_norm") or skw.get("track_grad_norm") else {}))
+                return call
+            return [o, ps, [p.grad for p in ps]], [o], [("step 1", step()), ("step 2, max_grad_norm", step(max_grad_norm=0.5, grad_scale=0.5)),
+                                  ("step 3, clip_value and track_grad_norm", step(clip_value=0.01, track_grad_norm=True)),
+                                  ("swap_ema", lambda: o.swap_ema() or state()), ("swap_ema back", lambda: o.swap_ema() or state())]
+        return build
+
+    ema = dict(ema_decay=0.9)
+    forced = dict(ema, force_exchange=True, bucket_bytes=64 << 10)
+    return [
+        ("1a EDM on the tiny UNet, fused Adam + EMA", train("edm", tiny, **ema)),
+        ("1b consistency model, fused RAdam + EMA, max_steps=6", train("cm", max_steps=6, **ema)),
+        ("1c autoencoder, fused AdamW + EMA", train("ae", **ema)),
+        ("2a EDM, gradient_clip_val by norm", train("edm", gradient_clip_val=0.05, **ema)),
+        ("2b EDM, gradient_clip_val by value", train("edm", gradient_clip_val=0.01, gradient_clip_algorithm="value", **ema)),
+        ("2c EDM, track_grad_norm alone", train("edm", track_grad_norm=True, **ema)),
+        ("3a EDM, force_exchange over one gloo rank, overlap=True", train("edm", overlap=True, **forced)),
+        ("3b EDM, force_exchange over one gloo rank, overlap=False", train("edm", overlap=False, **forced)),
+        ("4 validate and ema_weights()", evaluate()),
+        ("5 save_checkpoint, load_checkpoint into a fresh trainer, one step", resume()),
+        ("6 EDM, fused_optimizer=False + EMA (plan launches and collectives only)", train("edm", fused_optimizer=False, **ema)),
+        ("7a FusedAdamEMA alone, weight_decay", bare(FusedAdamEMA, weight_decay=1e-2)),
+        ("7b FusedRAdamEMA alone", bare(FusedRAdamEMA)),
+    ]
+
+
+def trainer_listing(out, outputs):
+    import torch.distributed as dist
+
+    from tqdne_amd import _lib, engine, rng
+    from tqdne_amd._lib import TqAdamChunk
+    rec = _lib._LIB = Recorder(_lib.load(), _lib._PROTOS)
+    dist.init_process_group("gloo", store=dist.HashStore(), rank=0, world_size=1)   # (for the force_exchange cases)
+
+    def gather_all(names, roots):
+        names.seen.clear()
+        names.ranges.clear()   # (only what is held NOW: the range of a freed storage would claim whatever is allocated there next)
+        for o in roots:
+            names.gather(o)
+            m = getattr(o, "module", None)
+            if isinstance(m, torch.nn.Module):   # (a module hands its parameters over; gradients, scratch cache and plans are looked up)
+                names.gather([p.grad for p in m.parameters()])
+                names.gather(getattr(m, "_scal", None))
+                for sm in m.modules():
+                    for e in sm.__dict__.get("_engine_cache", {}).values():
+                        names.gather(e)
+                        names.gather(e._bwd)
+        names.gather(list(engine._PACK_TABLES.values()))
+
+    def table(names, t, n):
+        """decoded rows of a device chunk table, addresses resolved; (lines, rows as integers: buffer number | -1, offset, ..., n)"""
+        if t is None or not n:
+            return [], torch.zeros(0, 11, dtype=torch.int64)
+        lines, rows = [], []
+        for r in (TqAdamChunk * n).from_buffer_copy(bytes(t.cpu().tolist())):
+            txt = [names.arg(("ptr", getattr(r, f) or 0)) for f in ("p", "g", "m", "v", "ema")]
+            lines.append(" ".join(f"{f}={x}" for f, x in zip("p g m v ema".split(), txt)) + f" n={r.n}")
+            where = [re.fullmatch(r"buf(\d+)\+(\d+)", x) for x in txt]
+            rows.append([int(v) for w in where for v in (w.groups() if w else (-1, 0))] + [r.n])
+        return lines, torch.tensor(rows, dtype=torch.int64)
+
+    with Collectives(rec):
+        for title, build in trainer_cases():
+            out.write(f"==== case {title}\n")
+            roots = opts = calls = names = None   # (every case starts from an empty allocator, see model_listing)
+            gc.collect()
+            torch.cuda.empty_cache()
+            torch.manual_seed(0)
+            rng.seed_rank(0)
+            rec.log = []
+            roots, opts, calls = build()          # (the constructor's broadcast belongs to the listing)
+            names, written = Names(), {}
+            for tag, call in [("construction", dict)] + calls:
+                if tag != "construction":
+                    rec.log = []
+                res = call()
+                torch.cuda.synchronize()
+                log, rec.log = rec.log, None
+                roots.append(res)
+                names.tmp = {}
+                gather_all(names, roots)
+                out.write(f"-- calls: {tag}\n")
+                streams = {}
+                for name, args in log:
+                    if name[0] == "@":
+                        out.write(f"     collective {name[1:]} of {args[1]} x {args[0]}, async_op={args[2]}\n")
+                    else:
+                        s = stream_of(args)
+                        if name == "tq_pack_jobs":   # (its job table is uploaded for this one launch and freed: whatever is allocated
+                            args = [0] + args[1:]    # at that address later in the call must not lend it its name)
+                        out.write(f"     {names.call(name, args[:-1])} on stream {streams.setdefault(s, len(streams))}\n")
+                for i, o in enumerate(opts):
+                    for what, t, n in (("step", o._table, getattr(o, "_n_chunks", 0)), ("swap", o._swap_table, getattr(o, "_swap_chunks", 0))):
+                        lines, rows = table(names, t, n)
+                        same = written.get((i, what)) == lines   # (written out when it changes, compared after every call)
+                        out.write(f"-- optimizer {i}, {what} table: {len(lines)} rows{', as written above' if same and lines else ''}\n")
+                        if not same:
+                            out.writelines(f"     {l}\n" for l in lines)
+                            written[i, what] = lines
+                            outputs[f"{title} / {tag} / optimizer {i} {what} table"] = rows
+                for k, v in res.items():
+                    outputs[f"{'~' if k[0] == '~' else ''}{title} / {tag} / {k.lstrip('~')}"] = v.detach().clone().cpu()
+    dist.destroy_process_group()
+
+
 def movable_last(path):
     """the listing with the lines that may move (see --diff) put at the end of the run they belong to -- so a run that lost or gained one
     still differs -- and the buffers renumbered in that order of appearance within each case"""
@@ -492,10 +721,10 @@ if __name__ == "__main__":
             diff = {k: float((a[k].double() - b[k].double()).abs().max()) for k in loose if not torch.equal(a[k], b[k])}
             print(f"{len(loose)} losses / gradients, {len(diff)} not bit-equal, largest difference {max(diff.values(), default=0.0):.3e}")
         sys.exit(1 if bad else 0)
-    models = sys.argv[1] == "--models"
-    argv = sys.argv[2:] if models else sys.argv[1:]
+    mode = {"--models": model_listing, "--trainer": trainer_listing}.get(sys.argv[1])
+    argv = sys.argv[2:] if mode else sys.argv[1:]
     outs = {}
     with open(argv[0], "w") as f:
-        (model_listing if models else listing)(f, outs)
+        (mode or listing)(f, outs)
     if len(argv) > 1:
         torch.save(outs, argv[1])

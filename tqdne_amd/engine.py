@@ -350,6 +350,15 @@ def shared_range_flag(model, device) -> torch.Tensor:
     return flags[key]
 
 
+def leave_fp16_range_scheme(model):
+    """Move ``model`` and every plan it holds to the fp32-range bf16x3 scheme: after the range guard fired (``_range_fallback``), or
+    when a run that had left the fp16-range scheme is resumed (DataParallelTrainer.load_checkpoint)."""
+    model._conv_scheme = "bf16x3"           # plans built later start there
+    for eng in getattr(model, "_engine_cache", {}).values():
+        if eng.scheme == "auto":
+            eng._set_scheme_bf16x3()
+
+
 class Probe:
     """HIP-event timings of one op of the plan (events are recorded on the stream the kernel is launched on)."""
 
@@ -1025,11 +1034,8 @@ class UNetEngine:
         warnings.warn("tqdne_amd: activations approach the fp16 range (a tensor's 128-position sum of squares reached (65504/2)^2); "
                       "the forward convolutions of this model now run in the fp32-range bf16x3 scheme", RuntimeWarning)
         self.range_flag.zero_()
-        self.m._conv_scheme = "bf16x3"           # plans built later start there
-        for eng in getattr(self.m, "_engine_cache", {}).values():
-            if eng.scheme == "auto":
-                eng._set_scheme_bf16x3()
-        if self.scheme == "auto":
+        leave_fp16_range_scheme(self.m)
+        if self.scheme == "auto":                # (a plan its model's cache does not hold)
             self._set_scheme_bf16x3()
 
     def check_range(self) -> bool:

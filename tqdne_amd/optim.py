@@ -30,7 +30,9 @@ from ._lib import TQ_ADAM_CHUNK, TqAdamChunk, check
 class _FusedFlatOptimizer(torch.optim.Optimizer):
     """What the one-launch optimizers share: flat moment / EMA buffers, the device chunk table, the step's bookkeeping and torch's
     state format (``step``, ``exp_avg``, ``exp_avg_sq``: Adam's and RAdam's alike), gradient clipping / norm tracking in front of
-    the launch.  A subclass supplies ``_launch``."""
+    the launch, and the choice between the guarded and the clipped entry point (``_launch``).  A subclass supplies ``_entry`` = (guarded
+    entry point, clipped entry point, what ``check`` calls the launch) and ``_scalars(t, group, ema_w, grad_scale)``, the launch's
+    scalars between the chunk count and the skip pointer."""
 
     def __init__(self, named_params: Iterable[Tuple[str, torch.nn.Parameter]], lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, ema_decay: Optional[float] = None, weight_decay: float = 0.0):
@@ -66,10 +68,13 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
             n = p.numel()
             self.state[p] = dict(step=self._step_t, exp_avg=self._m[o:o + n].view_as(p),
                                  exp_avg_sq=self._v[o:o + n].view_as(p))
-        self._table = None
+        self._table = None           # the step's table: rows of the parameters that have a gradient (``_build_table``)
         self._table_key = None
+        self._n_chunks = 0
+        self._updated = []           # the parameters of ``_table``: the ones whose versions a step bumps
         self._swap_table = None      # the swap's own table, made by the first ``swap_ema``
         self._swap_key = None
+        self._swap_chunks = 0
         self._norm_buf = None        # (fp64 partials per chunk, [norm, coefficient]) of the current table, made on first use
         self.last_grad_norm = None   # device fp32 scalar once a step has formed the norm
 
@@ -92,22 +97,6 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         for n, t in self.ema_state().items():
             t.copy_(ema_state[n])
 
-    def _build_swap_table(self):
-        """(p, ema, n) rows over EVERY optimized parameter, g / m / v null: unlike the step's table it does not depend on ``p.grad``
-        (which skips parameters without a gradient and does not exist before the first step)"""
-        ps = self.param_groups[0]["params"]
-        rows = []
-        for p, o in zip(ps, self._offs):
-            n = p.numel()
-            for s in range(0, n, TQ_ADAM_CHUNK):
-                rows.append((p.data_ptr() + 4 * s, self._ema.data_ptr() + 4 * (o + s), min(TQ_ADAM_CHUNK, n - s)))
-        arr = (TqAdamChunk * len(rows))()
-        for i, r in enumerate(rows):
-            arr[i].p, arr[i].ema, arr[i].n = r
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self._swap_table = host.to(self._m.device)
-        self._swap_chunks = len(rows)
-
     @torch.no_grad()
     def swap_ema(self):
         """Exchange every optimized parameter with its EMA in place: ONE launch (tq_ema_swap) on the current stream, no second copy of
@@ -121,7 +110,8 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         ps = self.param_groups[0]["params"]
         key = tuple(p.data_ptr() for p in ps)
         if key != self._swap_key:
-            self._build_swap_table()
+            # (EVERY optimized parameter: unlike the step's table it does not depend on ``p.grad``, which may not exist yet)
+            self._swap_table, self._swap_chunks = self._upload(self._rows(grads=False))
             self._swap_key = key
         stream = torch.cuda.current_stream(self._m.device).cuda_stream
         check(self._lib.tq_ema_swap(self._swap_table.data_ptr(), self._swap_chunks, stream), "ema swap")
@@ -129,32 +119,38 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         self.ema_swapped = not self.ema_swapped
 
     # ------------------------------------------------------------------ chunk table
-    def _build_table(self):
-        ps = self.param_groups[0]["params"]
-        rows = []
-        for p, o in zip(ps, self._offs):
-            if p.grad is None:
-                continue  # like torch: parameters without a gradient are skipped
-            g = p.grad
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients")
+    def _rows(self, grads: bool):
+        """(p, g, m, v, ema, n) addresses of every chunk of ``TQ_ADAM_CHUNK`` elements, 0 for null.  ``grads``: the step's rows, of the
+        parameters that have a gradient; otherwise every parameter with g / m / v null (the swap's rows)."""
+        def at(t, elem):
+            return 0 if t is None else t.data_ptr() + 4 * elem
+        for p, o in zip(self.param_groups[0]["params"], self._offs):
+            g = m = v = None
+            if grads:
+                if p.grad is None:
+                    continue  # like torch: parameters without a gradient are skipped
+                g, m, v = p.grad, self._m, self._v
+                if g.dtype != torch.float32 or not g.is_contiguous():
+                    raise ValueError(f"{type(self).__name__} needs contiguous fp32 gradients")
             n = p.numel()
             for s in range(0, n, TQ_ADAM_CHUNK):
-                c = min(TQ_ADAM_CHUNK, n - s)
-                rows.append((p.data_ptr() + 4 * s, g.data_ptr() + 4 * s, self._m.data_ptr() + 4 * (o + s),
-                             self._v.data_ptr() + 4 * (o + s), 0 if self._ema is None else self._ema.data_ptr() + 4 * (o + s), c))
-        arr = (TqAdamChunk * len(rows))()
-        for i, r in enumerate(rows):
-            arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].ema, arr[i].n = r[0], r[1], r[2], r[3], r[4] or None, r[5]
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self._table = host.to(self._m.device)
-        self._n_chunks = len(rows)
-        self._norm_buf = None
-        self._updated = [p for p in ps if p.grad is not None]
+                yield at(p, s), at(g, s), at(m, o + s), at(v, o + s), at(self._ema, o + s), min(TQ_ADAM_CHUNK, n - s)
 
-    def _key(self):
+    def _upload(self, rows):
+        """rows -> (the device table of ``TqAdamChunk``, their number)"""
+        rows = list(rows)
+        arr = (TqAdamChunk * len(rows))(*(TqAdamChunk(*r) for r in rows))
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self._m.device), len(rows)
+
+    def _build_table(self):
+        """the step's table, rebuilt when a parameter or its gradient has moved"""
         ps = self.param_groups[0]["params"]
-        return tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in ps)
+        key = tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in ps)
+        if key != self._table_key:
+            self._table, self._n_chunks = self._upload(self._rows(grads=True))
+            self._table_key = key
+            self._norm_buf = None   # (sized by the table)
+            self._updated = [p for p in ps if p.grad is not None]
 
     # ------------------------------------------------------------------ step
     @torch.no_grad()
@@ -173,36 +169,17 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         clipping; a view of a buffer the next such step overwrites; never synchronised here).  ``skip_flag`` keeps its meaning: a
         raised flag drops the whole update, and the norm of such a step may be inf.  With none of the three given the step issues
         exactly the launch it always did."""
-        if max_grad_norm is not None and clip_value is not None:
-            raise ValueError("max_grad_norm and clip_value are alternatives (gradient_clip_algorithm 'norm' or 'value'): give one")
-        for name, val in (("max_grad_norm", max_grad_norm), ("clip_value", clip_value)):
-            if val is not None and not val > 0:
-                raise ValueError(f"{name} must be positive, got {val!r}")
-        if self.ema_swapped:
-            raise RuntimeError("the parameters hold the EMA weights (swap_ema / DataParallelTrainer.ema_weights): a step now would "
-                               "update the EMA as if it were the weights; swap back first")
+        self._check_step_args(max_grad_norm, clip_value)
         loss = closure() if closure is not None else None
-        key = self._key()
-        if key != self._table_key:
-            self._build_table()
-            self._table_key = key
+        self._build_table()
         self._step += 1
         t = self._step
         if self._n_chunks:
             ema_w = 0.0 if self.ema_decay is None else 1.0 - self.ema_decay
             stream = torch.cuda.current_stream(self._m.device).cuda_stream
-            clip = None
+            clip = None   # (device pointer of the norm-clipping coefficient | None, clip_value | 0.0)
             if max_grad_norm is not None or track_grad_norm:
-                if self._norm_buf is None:
-                    self._norm_buf = (torch.empty(self._n_chunks, dtype=torch.float64, device=self._m.device),
-                                      torch.empty(2, dtype=torch.float32, device=self._m.device))
-                partials, out = self._norm_buf
-                check(self._lib.tq_grad_sumsq(self._table.data_ptr(), self._n_chunks, partials.data_ptr(), stream), "grad_sumsq")
-                check(self._lib.tq_grad_clip_coef(partials.data_ptr(), self._n_chunks, grad_scale, max_grad_norm or 0.0,
-                                                  out.data_ptr(), stream), "grad_clip_coef")
-                self.last_grad_norm = out[0]
-                if max_grad_norm is not None:
-                    clip = (out.data_ptr() + 4, 0.0)
+                clip = self._form_norm(grad_scale, max_grad_norm, stream)
             if clip_value is not None:
                 clip = (None, float(clip_value))
             self._launch(t, self.param_groups[0], ema_w, grad_scale, None if skip_flag is None else skip_flag.data_ptr(), stream,
@@ -212,6 +189,38 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         torch._C._increment_version(self._updated)
         self._step_t.fill_(float(t))
         return loss
+
+    def _check_step_args(self, max_grad_norm, clip_value):
+        """the refusals in front of everything else (they read no instance state: ``ema_swapped`` is a class attribute)"""
+        if max_grad_norm is not None and clip_value is not None:
+            raise ValueError("max_grad_norm and clip_value are alternatives (gradient_clip_algorithm 'norm' or 'value'): give one")
+        for name, val in (("max_grad_norm", max_grad_norm), ("clip_value", clip_value)):
+            if val is not None and not val > 0:
+                raise ValueError(f"{name} must be positive, got {val!r}")
+        if self.ema_swapped:
+            raise RuntimeError("the parameters hold the EMA weights (swap_ema / DataParallelTrainer.ema_weights): a step now would "
+                               "update the EMA as if it were the weights; swap back first")
+
+    def _form_norm(self, grad_scale, max_grad_norm, stream):
+        """The two small launches that form ``[norm, coefficient]`` of the current table's gradients; ``last_grad_norm`` becomes a
+        view of the first.  Returns the launch's ``clip``: the second's address when ``max_grad_norm`` clips, None when it only tracks."""
+        if self._norm_buf is None:
+            self._norm_buf = (torch.empty(self._n_chunks, dtype=torch.float64, device=self._m.device),
+                              torch.empty(2, dtype=torch.float32, device=self._m.device))
+        partials, out = self._norm_buf
+        check(self._lib.tq_grad_sumsq(self._table.data_ptr(), self._n_chunks, partials.data_ptr(), stream), "grad_sumsq")
+        check(self._lib.tq_grad_clip_coef(partials.data_ptr(), self._n_chunks, grad_scale, max_grad_norm or 0.0,
+                                          out.data_ptr(), stream), "grad_clip_coef")
+        self.last_grad_norm = out[0]
+        return (out.data_ptr() + 4, 0.0) if max_grad_norm is not None else None
+
+    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream, clip=None):
+        guarded, clipped, what = self._entry
+        args = (self._table.data_ptr(), self._n_chunks, *self._scalars(t, g, ema_w, grad_scale), skip_ptr)
+        if clip is None:
+            check(getattr(self._lib, guarded)(*args, stream), what)
+        else:
+            check(getattr(self._lib, clipped)(*args, clip[0], clip[1], stream), what + " (clipped)")
 
     # ------------------------------------------------------------------ (de)serialisation in torch Adam's format
     def state_dict(self):
@@ -242,16 +251,13 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
 class FusedAdamEMA(_FusedFlatOptimizer):
     """``weight_decay`` > 0 gives torch.optim.AdamW (decoupled decay), the autoencoder's optimizer (autoencoder.py:93-95)."""
 
-    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream, clip=None):
+    _entry = ("tq_adam_ema_step_guarded", "tq_adam_ema_step_clipped", "adam")
+
+    def _scalars(self, t, g, ema_w, grad_scale):
         b1, b2 = g["betas"]
         step_size = g["lr"] / (1.0 - b1 ** t)
         ibc2 = 1.0 / math.sqrt(1.0 - b2 ** t)
-        args = (self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], ibc2, ema_w, grad_scale,
-                1.0 - g["lr"] * g["weight_decay"], skip_ptr)
-        if clip is None:
-            check(self._lib.tq_adam_ema_step_guarded(*args, stream), "adam")
-        else:   # (device pointer of the norm-clipping coefficient | None, clip_value | 0.0)
-            check(self._lib.tq_adam_ema_step_clipped(*args, clip[0], clip[1], stream), "adam (clipped)")
+        return step_size, b1, b2, g["eps"], ibc2, ema_w, grad_scale, 1.0 - g["lr"] * g["weight_decay"]
 
 
 def radam_scalars(t: int, lr: float, b1: float, b2: float):
@@ -275,11 +281,9 @@ class FusedRAdamEMA(_FusedFlatOptimizer):
             raise ValueError("FusedRAdamEMA implements torch.optim.RAdam without weight decay (the consistency model's optimizer)")
         super().__init__(named_params, lr=lr, betas=betas, eps=eps, ema_decay=ema_decay, weight_decay=0.0)
 
-    def _launch(self, t, g, ema_w, grad_scale, skip_ptr, stream, clip=None):
+    _entry = ("tq_radam_ema_step_guarded", "tq_radam_ema_step_clipped", "radam")
+
+    def _scalars(self, t, g, ema_w, grad_scale):
         b1, b2 = g["betas"]
         step_size, rect = radam_scalars(t, g["lr"], b1, b2)
-        args = (self._table.data_ptr(), self._n_chunks, step_size, b1, b2, g["eps"], rect, ema_w, grad_scale, skip_ptr)
-        if clip is None:
-            check(self._lib.tq_radam_ema_step_guarded(*args, stream), "radam")
-        else:
-            check(self._lib.tq_radam_ema_step_clipped(*args, clip[0], clip[1], stream), "radam (clipped)")
+        return step_size, b1, b2, g["eps"], rect, ema_w, grad_scale

@@ -26,6 +26,9 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import checkpoint, rng
+from .engine import leave_fp16_range_scheme, reserve_side_streams, shared_range_flag
+
 
 def init_process_group(backend: str = "nccl", device=None, **kw):
     """``torch.distributed.init_process_group`` with the one ordering rule this package has on ROCm: the sampler lanes and the
@@ -34,9 +37,13 @@ def init_process_group(backend: str = "nccl", device=None, **kw):
     queue and the training step of the paper UNet runs 22.1 -> 28.1 ms (measured with a forced one-rank exchange,
     ``profiles/r04_u_rccl_ab.txt``).  Extra keywords go to torch (``rank``, ``world_size``, ``timeout``, ``device_id`` ...)."""
     if device is not None and torch.device(device).type == "cuda":
-        from .engine import reserve_side_streams
         reserve_side_streams(torch.device(device))
     return dist.init_process_group(backend, **kw)
+
+
+def _flats(flat) -> list:
+    """a flat gradient buffer, or a list of them (the autoencoder step returns per-tensor gradients), as a list"""
+    return list(flat) if isinstance(flat, (list, tuple)) else [flat]
 
 
 def allreduce_mean_(flat, world_size: int, bucket_elems: int = 8 << 20, scale: bool = True):
@@ -44,7 +51,7 @@ def allreduce_mean_(flat, world_size: int, bucket_elems: int = 8 << 20, scale: b
     CPU tests), launched asynchronously and waited together, then one scale.  62 MB of gradients = 2 buckets of 32 MB."""
     if world_size <= 1:
         return flat
-    flats = list(flat) if isinstance(flat, (list, tuple)) else [flat]  # (the autoencoder step returns per-tensor gradients)
+    flats = _flats(flat)
     works = []
     for f in flats:
         f1 = f.view(-1)
@@ -76,6 +83,38 @@ class _Done:
 
     def wait(self):
         return True
+
+
+class _ForeachEMA:
+    """The EMA of a run on a torch optimizer, behind the surface the one-launch optimizers have for theirs (optim.py: ``ema_state``,
+    ``load_ema_state``, ``swap_ema``) plus the per-step ``lerp`` that those do inside their launch."""
+
+    def __init__(self, module, decay: float):
+        self.decay = decay
+        self.params = [p for p in module.parameters() if p.requires_grad]
+        self.ema = {n: p.detach().clone() for n, p in module.named_parameters() if p.requires_grad}
+        self.saved = None   # the training weights while the module holds the EMA (between two ``swap_ema()`` calls)
+
+    @torch.no_grad()
+    def lerp(self):
+        torch._foreach_lerp_(tuple(self.ema.values()), tuple(self.params), 1 - self.decay)
+
+    def ema_state(self):
+        return self.ema   # (``swap_ema`` copies it into the module and leaves the dict alone: always the EMA of the run)
+
+    def load_ema_state(self, src):
+        for n, t in self.ema.items():
+            t.copy_(src[n])
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """EMA weights into the module, or the training weights back: ``torch._foreach_copy_`` through one list of clones"""
+        if self.saved is None:
+            self.saved = [p.detach().clone() for p in self.params]
+            torch._foreach_copy_(self.params, list(self.ema.values()))
+        else:
+            torch._foreach_copy_(self.params, self.saved)
+            self.saved = None
 
 
 class DataParallelTrainer:
@@ -127,27 +166,22 @@ class DataParallelTrainer:
         self.gradient_clip_algorithm = gradient_clip_algorithm
         self.track_grad_norm = bool(track_grad_norm)
         self.last_grad_norm = None
-        self._ema = None
         # (exact classes: a subclass may change the update)
-        if self.fused and type(self.optimizer) not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.RAdam):
+        kind = type(self.optimizer)
+        if self.fused and kind not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.RAdam):
             self.fused = False
         if self.fused:
             from .optim import FusedAdamEMA, FusedRAdamEMA
             g = self.optimizer.param_groups[0]
-            named = self._named_optimized(g["params"])
-            if isinstance(self.optimizer, torch.optim.RAdam):
-                self.optimizer = FusedRAdamEMA(named, lr=g["lr"], betas=g["betas"], eps=g["eps"], ema_decay=ema_decay,
-                                               weight_decay=g.get("weight_decay", 0.0))
-            else:
-                wd = g.get("weight_decay", 0.0) if isinstance(self.optimizer, torch.optim.AdamW) else 0.0
-                self.optimizer = FusedAdamEMA(named, lr=g["lr"], betas=g["betas"], eps=g["eps"], ema_decay=ema_decay,
-                                              weight_decay=wd)
+            self.optimizer = (FusedRAdamEMA if kind is torch.optim.RAdam else FusedAdamEMA)(
+                self._named_optimized(g["params"]), lr=g["lr"], betas=g["betas"], eps=g["eps"], ema_decay=ema_decay,
+                weight_decay=0.0 if kind is torch.optim.Adam else g.get("weight_decay", 0.0))
             if self.scheduler is not None:
                 op = module.optimizer_params
                 self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=op["max_steps"],
                                                                             eta_min=op["eta_min"])
-        elif ema_decay is not None:
-            self._ema = {n: p.detach().clone() for n, p in module.named_parameters() if p.requires_grad}
+        # the keeper of the EMA weights: the fused optimizer (its launch updates them), a _ForeachEMA beside a torch optimizer, or None
+        self._ema = None if ema_decay is None else self.optimizer if self.fused else _ForeachEMA(module, ema_decay)
         self.bucket_elems = max(1, bucket_bytes // 4)
         sig = inspect.signature(module.step_and_backward).parameters
         self._hooked = "on_bucket" in sig
@@ -193,12 +227,7 @@ class DataParallelTrainer:
                     flat.copy_(h)
                 else:
                     dist.broadcast(flat, src=0, group=self.group)
-                o = 0
-                views = []
-                for p in ps:
-                    views.append(flat[o:o + p.numel()].view_as(p))
-                    o += p.numel()
-                torch._foreach_copy_(ps, views)
+                torch._foreach_copy_(ps, [v.view_as(p) for v, p in zip(flat.split([p.numel() for p in ps]), ps)])
 
     def _host_staged(self, t: torch.Tensor) -> bool:
         """device tensors over the gloo backend (the dry-run configuration of bench.py / the 1-GPU tests: ranks sharing a device) go
@@ -223,35 +252,29 @@ class DataParallelTrainer:
         works = []
         self.last_bucket_sizes = []
         self.last_tail_words = 0      # words of ours that rode at the end of the last gradient bucket (the range-guard pair: 2)
-        hook = None
-        if self.exchange and self.overlap and self._hooked:
-            def hook(sl):
-                self.last_bucket_sizes.append(sl.numel())
-                works.append(self._allreduce_async(sl))
+
+        def issue(sl):
+            self.last_bucket_sizes.append(sl.numel())
+            works.append(self._allreduce_async(sl))
+        hook = issue if self.exchange and self.overlap and self._hooked else None
+        kw = dict(on_bucket=hook, bucket_elems=self.bucket_elems) if self._hooked else {}   # (what the module's signature takes)
         tail = None
-        if hook is not None and self._tailed and self._skip_exchange_live():
+        if hook is not None and self._tailed and not self._skip_done and self._local_range_flag()[0] is not None:
             # the range-guard pair of this step rides at the end of the last gradient bucket (no collective of its own)
             tail = []
 
             def tail_fill(words):
-                self._skip_fill(words)
+                self._skip_fill(words, *self._local_range_flag())
                 tail.append(words)
                 self.last_tail_words = words.numel()
-        if self.max_steps is not None:
-            self.module._dp_progress = (self.steps_done, self.max_steps)
-        if tail is not None:
-            loss, flat = self.module.step_and_backward(batch, on_bucket=hook, bucket_elems=self.bucket_elems, tail_fill=tail_fill)
-        elif self._hooked:
-            loss, flat = self.module.step_and_backward(batch, on_bucket=hook, bucket_elems=self.bucket_elems)
-        else:
-            loss, flat = self.module.step_and_backward(batch)
+            kw["tail_fill"] = tail_fill
+        self._publish_progress()
+        loss, flat = self.module.step_and_backward(batch, **kw)
         if self.exchange and hook is None:
-            flats = list(flat) if isinstance(flat, (list, tuple)) else [flat]
-            for f in flats:
+            for f in _flats(flat):
                 f1 = f.view(-1)
                 for i in range(0, f1.numel(), self.bucket_elems):
-                    self.last_bucket_sizes.append(min(self.bucket_elems, f1.numel() - i))
-                    works.append(self._allreduce_async(f1[i:i + self.bucket_elems]))
+                    issue(f1[i:i + self.bucket_elems])
         reduced = tail[0] if tail else None
         if reduced is None:
             skip = self._range_skip_flag()
@@ -268,19 +291,21 @@ class DataParallelTrainer:
                 self.last_grad_norm = self.optimizer.last_grad_norm
         else:
             if self.world > 1:
-                flats = list(flat) if isinstance(flat, (list, tuple)) else [flat]
-                for f in flats:
+                for f in _flats(flat):
                     f.mul_(1.0 / self.world)
             self._clip_unfused()
             self.optimizer.step()
-            if self._ema is not None:
-                with torch.no_grad():
-                    named = dict(self.module.named_parameters())
-                    torch._foreach_lerp_(tuple(self._ema.values()), tuple(named[n] for n in self._ema), 1 - self.ema_decay)
+            if self._ema is not None:   # (the fused launch does this lerp itself)
+                self._ema.lerp()
         if self.scheduler is not None:
             self.scheduler.step()
         self.steps_done += 1
         return loss
+
+    def _publish_progress(self):
+        """``module._dp_progress`` for modules whose step depends on the run's progress (``max_steps`` in ``__init__``)"""
+        if self.max_steps is not None:
+            self.module._dp_progress = (self.steps_done, self.max_steps)
 
     def _clip_kwargs(self) -> dict:
         """the clipping / tracking arguments of the fused optimizer's step; empty with the defaults: the same call and the same launches as without these options"""
@@ -307,6 +332,7 @@ class DataParallelTrainer:
             torch.nn.utils.clip_grad_value_(ps, val)
 
     AGREE_EVERY = 64   # steps between the (host-synchronous) checks whether every rank has left the fp16-range scheme
+    _skip, _skip_steps, _skip_done = None, 0, False   # the exchange's state: the pair's buffer, steps so far, all ranks agreed to stop
 
     def _local_range_flag(self):
         """(device int32[1] range-guard flag of this rank's model | None, is this rank still on the fp16-range scheme?)"""
@@ -314,7 +340,6 @@ class DataParallelTrainer:
         if not self.fused or unet is None:
             return None, False
         dev = next(self.module.parameters()).device
-        from .engine import shared_range_flag
         return shared_range_flag(unet, dev), getattr(unet, "_conv_scheme", "auto") == "auto"
 
     def _range_skip_flag(self, reduced=None):
@@ -337,34 +362,28 @@ class DataParallelTrainer:
         ``reduced`` (round 5): the pair already summed over the ranks -- it rode at the end of the step's last gradient bucket
         (``tail_fill`` of BackwardPlan.run), so the step has no collective of its own for it; None: the pair is exchanged here (modules
         without the bucket hook, ``overlap=False``)."""
-        flag, auto = self._local_range_flag()
-        if flag is None:
-            return None
-        if not self.exchange:
-            return flag if auto else None
-        if getattr(self, "_skip_done", False):
-            return None
         if reduced is None:
+            flag, auto = self._local_range_flag()   # (read behind the step's forward, where a rank leaves the fp16-range scheme)
+            if flag is None:
+                return None
+            if not self.exchange:
+                return flag if auto else None
+            if self._skip_done:
+                return None
             # (summed as floats through the same exchange path as the gradients; the kernel tests word 0 for "non-zero", and a sum
             # of 0 / 1 flags has a non-zero bit pattern exactly when some rank raised its flag)
-            if getattr(self, "_skip", None) is None:
+            if self._skip is None:
                 self._skip = torch.zeros(2, dtype=torch.float32, device=flag.device)
-            self._skip_fill(self._skip)
+            self._skip_fill(self._skip, flag, auto)
             self._allreduce_async(self._skip).wait()
             reduced = self._skip
-        self._skip_steps = getattr(self, "_skip_steps", 0) + 1
+        self._skip_steps += 1
         if self._skip_steps % self.AGREE_EVERY == 0 and float(reduced[1].item()) >= self.world:
             self._skip_done = True
         return reduced
 
-    def _skip_exchange_live(self) -> bool:
-        """does this step exchange the range-guard pair? (fused optimizer on a 1-D UNet, exchange on, no agreement reached yet)"""
-        flag, _ = self._local_range_flag()
-        return flag is not None and self.exchange and not getattr(self, "_skip_done", False)
-
-    def _skip_fill(self, words):
+    def _skip_fill(self, words, flag, auto):
         """this rank's pair into ``words`` (2 floats): [its range-guard flag while it is on the fp16-range scheme, 1 once it left it]"""
-        flag, auto = self._local_range_flag()
         if auto:
             words[0:1].copy_(flag)
             words[1:2].zero_()
@@ -375,11 +394,9 @@ class DataParallelTrainer:
     def ema_state(self):
         """name -> EMA weights, as the reference's EMA callback stores them in a checkpoint (tqdne/ema.py:50-51).  Always the EMA of
         the training run, also inside ``ema_weights()`` (fused path: views of the parameters then, where the swap put the values)."""
-        if self.fused:
-            return self.optimizer.ema_state()
         if self._ema is None:
             raise RuntimeError("constructed without ema_decay")
-        return self._ema
+        return self._ema.ema_state()
 
     # ------------------------------------------------------------------ validation / prediction on the EMA weights
     _ema_active = False   # inside ``ema_weights()``
@@ -396,25 +413,13 @@ class DataParallelTrainer:
             raise RuntimeError("constructed without ema_decay")
         if self._ema_active:
             raise RuntimeError("ema_weights() is already active: the module holds the EMA weights (the context does not nest)")
-        saved = None
-        if self.fused:
-            self.optimizer.swap_ema()
-        else:
-            named = dict(self.module.named_parameters())
-            ps = [named[n] for n in self._ema]
-            with torch.no_grad():
-                saved = [p.detach().clone() for p in ps]
-                torch._foreach_copy_(ps, list(self._ema.values()))
+        self._ema.swap_ema()
         self._ema_active = True
         try:
             yield self.module
         finally:
             self._ema_active = False
-            if self.fused:
-                self.optimizer.swap_ema()
-            else:
-                with torch.no_grad():
-                    torch._foreach_copy_(ps, saved)
+            self._ema.swap_ema()
 
     @contextlib.contextmanager
     def _eval_pass(self):
@@ -442,8 +447,7 @@ class DataParallelTrainer:
             for i, batch in enumerate(batches):
                 if limit_batches is not None and i >= limit_batches:
                     break
-                if self.max_steps is not None:
-                    self.module._dp_progress = (self.steps_done, self.max_steps)
+                self._publish_progress()
                 loss = self.module.validation_step(batch, i)
                 B = batch["signal"].shape[0]
                 acc[0] += loss.detach().to(torch.float64) * B
@@ -467,13 +471,11 @@ class DataParallelTrainer:
         stopped, under ``EXTRA_KEY``: the dropout call counter, the conv scheme of the module's 1-D network and ``steps_done``."""
         if self._ema_active:
             raise RuntimeError("save_checkpoint inside ema_weights(): the module holds the EMA weights; leave the context first")
-        from . import rng
-        from .checkpoint import save_checkpoint
         net = self._network()
         extra = {self.EXTRA_KEY: {"dropout_counter": rng.dropout_counter(), "steps_done": self.steps_done,
                                   "conv_scheme": None if net is None else getattr(net, "_conv_scheme", "auto")}}
-        save_checkpoint(self.module, path, ema_state=self.ema_state() if self.ema_decay is not None else None,
-                        optimizer=self.optimizer, lr_scheduler=self.scheduler, epoch=epoch, global_step=self.steps_done, extra=extra)
+        checkpoint.save_checkpoint(self.module, path, ema_state=self.ema_state() if self.ema_decay is not None else None,
+                                   optimizer=self.optimizer, lr_scheduler=self.scheduler, epoch=epoch, global_step=self.steps_done, extra=extra)
 
     def load_checkpoint(self, path):
         """Put module, optimizer, EMA, scheduler and step count back where ``save_checkpoint`` -- or the reference's ModelCheckpoint --
@@ -483,20 +485,13 @@ class DataParallelTrainer:
         checkpoint dict."""
         if self._ema_active:
             raise RuntimeError("load_checkpoint inside ema_weights(): leave the context first")
-        from . import rng
-        from .checkpoint import load_checkpoint
-        ckpt = load_checkpoint(path, map_location="cpu")
+        ckpt = checkpoint.load_checkpoint(path, map_location="cpu")
         self.module.load_state_dict(ckpt["state_dict"])
         if ckpt.get("optimizer_states"):
             self.optimizer.load_state_dict(ckpt["optimizer_states"][0])
         if self.ema_decay is not None:
             with torch.no_grad():
-                src = ckpt.get("ema_state") or dict(self.module.named_parameters())
-                if self.fused:
-                    self.optimizer.load_ema_state(src)
-                else:
-                    for n, t in self._ema.items():
-                        t.copy_(src[n])
+                self._ema.load_ema_state(ckpt.get("ema_state") or dict(self.module.named_parameters()))
         if self.scheduler is not None and ckpt.get("lr_schedulers"):
             self.scheduler.load_state_dict(ckpt["lr_schedulers"][0])
         ours = ckpt.get(self.EXTRA_KEY) or {}
@@ -505,10 +500,7 @@ class DataParallelTrainer:
             rng.reset_dropout_counter(ours["dropout_counter"])
         net = self._network()
         if net is not None and ours.get("conv_scheme") == "bf16x3" and getattr(net, "_conv_scheme", "auto") == "auto":
-            net._conv_scheme = "bf16x3"   # (the run had left the fp16-range scheme: plans built from now on start there ...)
-            for eng in net._engine_cache.values():   # (... and the ones that exist move)
-                if eng.scheme == "auto":
-                    eng._set_scheme_bf16x3()
+            leave_fp16_range_scheme(net)   # (the run had left it: the plans that exist move, plans built from now on start there)
         return ckpt
 
     def fit(self, train_batches, val_batches=None, *, max_steps, val_check_interval=None, limit_val_batches=None, dirpath=None,
