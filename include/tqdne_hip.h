@@ -410,6 +410,11 @@ int tq_attention_bwd_hd(const float* qkv, const float* out, const float* dout, c
                         void* workspace, int B, int T, int H, int D, hipStream_t stream);
 
 /* ---- EDM / sampler elementwise ------------------------------------------------------------------------------ */
+/* Argument checks of the elementwise entry points of this section and the three below (DDPM, losses, VAE, concat), and of
+ * tq_fourier_features / tq_gemm_f32_jobs / tq_zero_stuff / tq_pair_sum: a NULL pointer that is not marked nullable, a non-positive
+ * B / size / count (n == 0 for the size_t ones) or channels that are not a multiple of 4 return TQ_ERR_ARG before the device is
+ * touched (tests/test_side_kernels_host.py).  tq_embed_fwd, tq_linear_fwd and tq_gn_bwd_finalize answer a NULL pointer with
+ * TQ_ERR_ARG and a shape they are not built for with TQ_ERR_SHAPE (tq_linear_fwd: E <= 511, the 160 KB of LDS). */
 /* per-sample scalars from sigma: c_in, c_out, c_skip, c_noise, loss weight  (edm.py:24-37); sigma_stride 0 = shared */
 int tq_edm_scalars(const float* sigma, int sigma_stride, float sigma_data, float* c_in, float* c_out, float* c_skip,
                    float* c_noise, float* lweight, int B, hipStream_t stream);

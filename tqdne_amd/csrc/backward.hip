@@ -1168,7 +1168,7 @@ extern "C" int tq_gn_bwd_apply_colsum(const float* g, const float* x, const floa
 }
 
 extern "C" int tq_zero_stuff(const float* dy, float* out, int B, int T_out, int T_in, int C, hipStream_t stream) {
-    if (!dy || !out || B <= 0 || T_out <= 0 || T_in <= 0 || C % 4) return TQ_ERR_ARG;
+    if (!dy || !out || B <= 0 || T_out <= 0 || T_in <= 0 || C <= 0 || C % 4) return TQ_ERR_ARG;
     const size_t n4 = (size_t)B * T_in * (C / 4);
     hipLaunchKernelGGL(zero_stuff_kernel, dim3(ew_grid4(n4)), dim3(256), 0, stream, dy, out, T_out, T_in, C, n4);
     TQ_CHECK_LAUNCH();
@@ -1176,7 +1176,7 @@ extern "C" int tq_zero_stuff(const float* dy, float* out, int B, int T_out, int 
 }
 
 extern "C" int tq_pair_sum(const float* d_up, float* dx, int B, int T, int C, int accumulate, hipStream_t stream) {
-    if (!d_up || !dx || B <= 0 || T <= 0 || C % 4) return TQ_ERR_ARG;
+    if (!d_up || !dx || B <= 0 || T <= 0 || C <= 0 || C % 4) return TQ_ERR_ARG;
     const size_t n4 = (size_t)B * T * (C / 4);
     hipLaunchKernelGGL(pair_sum_kernel, dim3(ew_grid4(n4)), dim3(256), 0, stream, d_up, dx, T, C, accumulate, n4);
     TQ_CHECK_LAUNCH();

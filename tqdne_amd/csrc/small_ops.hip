@@ -782,19 +782,40 @@ __global__ __launch_bounds__(256) void pseudo_huber_kernel(const float* __restri
 }
 
 // Mean squared error and its gradient (autoencoder.py:61-63): loss += sum (a - b)^2 / n, d = 2 (a - b) / n
-__global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ loss,
-                                                  float* __restrict__ d, size_t n, float inv_n) {
+// Every workgroup ends in one atomic add into the one float of loss_out, in the order the workgroups arrive, and the last digits of the
+// value move with that order: so few, large workgroups (at most MSE_WGS of MSE_NT threads), each thread walking MSE_UNROLL grid strides
+// per trip with all their loads in flight (DESIGN_LOG.md, 2026-10-20: spread of the value and time per call against the wide grid).
+constexpr unsigned MSE_WGS = 64;
+constexpr int MSE_NT = 1024;
+constexpr int MSE_UNROLL = 8;
+__global__ __launch_bounds__(MSE_NT) void mse_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ loss,
+                                                     float* __restrict__ d, size_t n, float inv_n) {
     float acc = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float df = a[i] - b[i];
-        acc += df * df;
-        if (d) d[i] = 2.0f * df * inv_n;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += MSE_UNROLL * stride) {
+        float df[MSE_UNROLL];
+#pragma unroll
+        for (int k = 0; k < MSE_UNROLL; ++k) {
+            const size_t j = i + k * stride;
+            df[k] = j < n ? a[j] - b[j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < MSE_UNROLL; ++k) {
+            const size_t j = i + k * stride;
+            acc += df[k] * df[k];
+            if (d && j < n) d[j] = 2.0f * df[k] * inv_n;
+        }
     }
     acc = wave_sum(acc);
-    __shared__ float ws[4];
+    __shared__ float ws[MSE_NT / 64];
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (ws[0] + ws[1] + ws[2] + ws[3]) * inv_n);
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < MSE_NT / 64; ++w) t += ws[w];   // (fixed order)
+        atomicAdd(loss, t * inv_n);
+    }
 }
 
 // VAE bottleneck (autoencoder.py:37-43, 64-66; blocks.py:233-260): enc (B, 2L, T) = [mean | log_std] on the channel axis.
@@ -1000,7 +1021,8 @@ extern "C" int tq_mse_loss(const float* a, const float* b, float* loss_out, floa
     if (!a || !b || !loss_out || n == 0) return TQ_ERR_ARG;
     hipError_t e = hipMemsetAsync(loss_out, 0, sizeof(float), stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mse_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, b, loss_out, d, n, 1.0f / (float)n);
+    const size_t g = (n + MSE_NT - 1) / MSE_NT;
+    hipLaunchKernelGGL(mse_kernel, dim3((unsigned)(g > MSE_WGS ? MSE_WGS : g)), dim3(MSE_NT), 0, stream, a, b, loss_out, d, n, 1.0f / (float)n);
     TQ_CHECK_LAUNCH();
     return 0;
 }
