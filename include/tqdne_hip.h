@@ -57,16 +57,35 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* TqConvDesc.wfmt: how the fp32 product x * w is contracted on the matrix cores (= format of the packed weights).
  * BF16X3: both operands split into bf16 hi + lo, three bf16 MFMA products; fp32 range, ~2^-16 relative (pack modes 0 / 1).
+ *   RANGE, both operands: that of fp32 -- the error against exact arithmetic is 7e-6 ... 9e-6 of the output for weights of typical
+ *   magnitude 6e-2 down to 6e-11 and activations of 1e3 down to 1e-6 (measured; tests/test_contraction_gpu.py, range sweep).
  * F16_MX8: per 64 channels two fp16 MFMAs plus one block-scaled fp8 MFMA carrying both first-order corrections; ~2^-15 relative at
  * 2/3 of the MFMA cycles; the activation operand has fp16 RANGE (|x| > 65504 overflows to inf / NaN in the output, relative precision lost below 6e-5).  Built
  * for stride-1 forward launches (tq_conv1d_fwd, tq_conv1d_fwd_skip, tq_conv1d_fwd_qkv) with 128 | C_out and 64 | every source's
- * channels (pack mode 2). */
+ * channels (pack mode 2).
+ *   RANGE: the corrections are e4m3 with UNIFORM scales, so the ~2^-15 holds for O(1) operands only.  Activation operand: |x| <= 448
+ *   (beyond it the x w_l correction clamps: 3e-4 of the output at |x| ~ 1e3) and typical |x| >= ~0.1 (x_l 2^12 falls below e4m3's
+ *   normal range: 1.5e-4 at 1e-3, 2e-3 at 1e-5, 2e-2 at 1e-6).  WEIGHT operand (stored as fp16(w), e4m3(w) and e4m3(w_l 2^12), no
+ *   scale): typical |w| >= ~2e-2 and |w| <= 448 -- at typical |w| = 6e-5 the x_l w correction is gone (4e-4), at 6e-7 the error is
+ *   3e-2, at 6e-8 0.3, below that the output is zero.  |w| >= 65520 becomes inf. */
 #define TQ_WFMT_BF16X3 0
 #define TQ_WFMT_F16_MX8 1
 /* F16_MX6: as F16_MX8 with e2m3 (fp6) correction operands and per-lane E8M0 block scales (one per 16 channels): 12 instead of 16
  * MFMA passes per 64 channels and corrections that do not clamp; same shapes, same fp16 RANGE of the activation operand (pack
  * mode 3).  Round 6: additionally 64 | C_out for the k = 5 launches with a TQ_CONV_GN | TQ_CONV_SILU prologue (tq_conv1d_fwd,
- * tq_conv1d_fwd_skip: the 64-channel ResBlock convs; tile of 64 channels x 128 positions). */
+ * tq_conv1d_fwd_skip: the 64-channel ResBlock convs; tile of 64 channels x 128 positions).
+ *   RANGE (measured on the kernels and reproduced by the bit-model oracle/contraction.py; error against exact arithmetic relative to
+ *   the largest output).  Both operands' main part is a plain fp16 value with no scale; the block scales only serve the corrections,
+ *   which can restore what fp16's ROUNDING lost (11 -> ~15 bits) but not what its SUBNORMAL range lost.  Inside the envelope the
+ *   error is 1.1e-5 ... 1.5e-5:
+ *     activation operand: |x| <= 65504 (beyond: inf / NaN in the output), typical |x| >= 1e-3.  Below: 7e-5 at 1e-5, 7e-4 at 1e-6.
+ *     WEIGHT operand (pack modes 3 / 5 store fp16(w) un-scaled): |w| < 65520 (beyond: inf), typical |w| >= ~5e-5 (weight rms 5.6e-5:
+ *     1.3e-5).  Below: 1.2e-3 at rms 5.6e-7, 1.1e-2 at 5.6e-8, 3.6e-2 at 5.6e-9 and smaller (fp16(w) is zero there, the e2m3
+ *     corrections are all that is left).  One hot channel (x 1e3) inside a 16-block or 2 % of x 30 outliers on either operand stay
+ *     at 2e-5.
+ *   Zero-initialised convs (zero_module) pass through the range below the envelope during the first optimizer steps: their forward
+ *   output is then small against the residual path it is added to, but the DATA GRADIENT through them (pack mode 5, below) carries
+ *   the same relative error into everything upstream -- see TqConvBwdDesc.wfmt. */
 #define TQ_WFMT_F16_MX6 2
 
 /* ABI 7.  Consumer-side GroupNorm fold (TqConvDesc.gn_fold; optional, NULL = off): the launch forms the folded coefficients of ITS OWN
@@ -136,7 +155,10 @@ typedef struct TqConvBwdDesc {
      * TQ_WFMT_F16_MX6 (packed_w_t from pack mode 5; 64 | C_dy and 64 | C_dx0 + C_dx1): dy is staged times the exact power of two
      * that brings max|dy| into [2^13, 2^14) -- gradients are far below fp16's normal range otherwise -- and the accumulators are
      * multiplied by its inverse, so the result has the accuracy of the forward scheme (~2^-15 relative) at half the MFMA cycles of
-     * bf16x3.  dy_amax: DEVICE pointer to a TQ_AMAX_WORDS block as tq_colsum(..., amax_out) / tq_gn_bwd_apply_colsum fill it for the same
+     * bf16x3.  RANGE: dy is un-limited (it is scaled; samples of one batch that differ by 1e-6 in scale under the shared maximum still
+     * come out at 1.1e-5 of their own largest entry).  The WEIGHT operand is NOT scaled and has the envelope of TQ_WFMT_F16_MX6 above:
+     * typical |w| >= ~5e-5; measured error of the data gradient relative to its largest entry 1.2e-3 at weight rms 5.6e-7, 1.1e-2 at
+     * 5.6e-8, 4e-2 at 5.6e-9 and below, whatever the size of dy (TQ_WFMT_BF16X3: 8e-6 throughout).  dy_amax: DEVICE pointer to a TQ_AMAX_WORDS block as tq_colsum(..., amax_out) / tq_gn_bwd_apply_colsum fill it for the same
      * dy (the maximum over its TQ_AMAX_WAYS words = IEEE bit pattern of max|dy|; any upper bound within a factor 8 will do); required for
      * TQ_WFMT_F16_MX6. */
     int32_t wfmt;

@@ -123,8 +123,10 @@ def unet_layout(cfg: dict):
 # leaf ops
 # --------------------------------------------------------------------------
 def group_norm32(sd: SD, p: str, x: Tensor) -> Tensor:
-    # nn.py:11-13 -- computed on x.float(), cast back
-    return F.group_norm(x.float(), GN_GROUPS, sd[p + ".weight"], sd[p + ".bias"], GN_EPS).type(x.dtype)
+    # nn.py:11-13 -- computed on x.float(), cast back (a float64 run of the oracle, the high-precision reference of some tests, stays in
+    # float64: the up-cast is there for half-precision activations)
+    xf = x if x.dtype == torch.float64 else x.float()
+    return F.group_norm(xf, GN_GROUPS, sd[p + ".weight"], sd[p + ".bias"], GN_EPS).type(x.dtype)
 
 
 def conv_same(sd: SD, p: str, x: Tensor) -> Tensor:
