@@ -613,6 +613,43 @@ int tq_envelope_fwd(const float* x, float* out, int N, int C, int T, int window,
 /* repr (N, 2C, T) -> waveform (N, C, T): scaled * (exp(log_env + log(log_eps)/2) + eps)   (representation.py:56-59) */
 int tq_envelope_inv(const float* repr, float* out, int N, int C, int T, double log_eps, double eps, hipStream_t stream);
 
+/* ---- classifier head and its loss (csrc/classifier.hip; added under ABI 8; classifier.py:39-64) ------------------ */
+/* The head behind the encoder's output conv, read where that conv left it: h (B, T, C) channels-last, contiguous.
+ *   pooled[b, c] = (sum_t h[b, t, c]) / T;   a1 = W1 silu(pooled) + b1;   emb = W2 silu(a1) + b2;   logits = W3 emb + b3
+ * W1, W2 (C, C), W3 (K, C) row-major as nn.Linear keeps them; pooled, a1 (pre-activation), emb (B, C) and logits (B, K) are
+ * overwritten.  Exact fp32 (FMA, expf, true division), fp32 accumulation; every sum runs in an order that depends on (T, C, K) alone
+ * and there are no atomics, so two calls on the same inputs give the same bits -- in all three entry points.  One workgroup per
+ * sample (any B).  Every pointer must be 16-byte aligned.
+ * Limits, answered without a device: 32 | C <= tq_classifier_head_max_channels() = 1024, K <= tq_classifier_head_max_classes() = 1024
+ * (the reference trains 36 classes).
+ * Argument checks, before the device is touched: a NULL pointer that is not marked nullable or a non-positive B / T / C / K returns
+ * TQ_ERR_ARG (checked first); a C that is not a multiple of 32 or above the limit, or a K above the limit, TQ_ERR_SHAPE.
+ *   tq_classifier_head_fwd: logits nullable (embed() only: W3, b3 and K are then not read and may be NULL / anything).
+ *   tq_cross_entropy: torch.nn.functional.cross_entropy(logits, labels, weight, ignore_index, reduction='mean'):
+ *       loss = sum_i w[y_i] nll_i / sum_i w[y_i] over the labels that are not ignored, nll_i = log sum_k exp(x_ik - max_k x_ik) + max_k x_ik
+ *       - x_i,y_i;  dlogits[i, k] = w[y_i] (softmax(x_i)[k] - [k == y_i]) / sum_i w[y_i], and zero in the rows of ignored labels.
+ *     labels int64 (B); weight (K) nullable (= 1); loss_out (1 float) overwritten; dlogits (B, K) nullable.  The per-sample terms are in
+ *     fp32, their sums over the samples in fp64, by a fixed tree of one workgroup.  A label outside [0, K) that is not ignore_index is
+ *     treated as ignored (torch raises; the device cannot).  A batch in which EVERY label is ignored returns loss = NaN (0 / 0, as
+ *     torch does) and dlogits = 0.
+ *   tq_classifier_head_bwd: from dlogits (B, K) and the saved pooled / a1 / emb of the forward: dW3 (K, C), db3 (K), dW2, dW1 (C, C),
+ *     db2, db1 (C) -- sums over the samples b = 0 .. B-1 in order, OVERWRITTEN, not accumulated -- and dh[b, t, c] = dpooled[b, c] / T,
+ *     (B, T, C) channels-last: the gradient buffer of the encoder's output conv.  Three launches (per-sample chain, weight gradients,
+ *     broadcast).  W3 == NULL: `dlogits` is d emb (B, C) itself (the backward of embed()); dW3 / db3 are not written and K is not read.
+ *     workspace: tq_classifier_head_bwd_workspace(B, C) bytes (5 B C floats; 0 for a non-positive B / C), 16-byte
+ *     aligned; fewer workspace_bytes than that: TQ_ERR_ARG. */
+int tq_classifier_head_max_channels(void);
+int tq_classifier_head_max_classes(void);
+size_t tq_classifier_head_bwd_workspace(int B, int C);
+int tq_classifier_head_fwd(const float* h, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                           const float* b3, float* pooled, float* a1, float* emb, float* logits, int B, int T, int C, int K,
+                           hipStream_t stream);
+int tq_cross_entropy(const float* logits, const int64_t* labels, const float* weight, int64_t ignore_index, float* loss_out,
+                     float* dlogits, int B, int K, hipStream_t stream);
+int tq_classifier_head_bwd(const float* dlogits, const float* pooled, const float* a1, const float* emb, const float* W1,
+                           const float* W2, const float* W3, float* dW3, float* db3, float* dW2, float* db2, float* dW1, float* db1,
+                           float* dh, void* workspace, size_t workspace_bytes, int B, int T, int C, int K, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,8 +16,13 @@ from .consistency_model import LithningConsistencyModel
 from .diffusion import DDPMScheduler, LightningDDMP
 from .edm import EDM, LightningEDM
 from .unet import UNetModel
+from .classifier import LithningClassifier
+from .metric import (AmplitudeSpectralDensity, FrechetInceptionDistance, InceptionScore, MeanSquaredError, Metric, NeuralMetric,
+                     frechet_distance)
 
 __version__ = "0.1.0"
 __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler", "LithningConsistencyModel", "LightningAutoencoder", "Encoder", "Decoder", "get_1d_unet_config",
            "get_1d_autoencoder_configs", "get_2d_unet_config", "get_2d_autoencoder_configs", "paper_1d_unet_config",
            "tiny_1d_unet_config"]
+__all__ += ["LithningClassifier", "frechet_distance", "Metric", "MeanSquaredError", "AmplitudeSpectralDensity", "NeuralMetric",
+            "FrechetInceptionDistance", "InceptionScore"]

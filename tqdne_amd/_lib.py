@@ -225,6 +225,12 @@ _PROTOS = {
     "tq_avg_pool2_fwd": (I, [VP, VP, VP, I, I, I, VP]),
     "tq_nearest_up2_fwd": (I, [VP, VP, VP, I, I, I, VP]),
     "tq_avg_pool2_bwd": (I, [VP, VP, I, I, I, I, VP]),
+    "tq_classifier_head_max_channels": (I, []),
+    "tq_classifier_head_max_classes": (I, []),
+    "tq_classifier_head_bwd_workspace": (SZ, [I, I]),
+    "tq_classifier_head_fwd": (I, [VP] * 11 + [I] * 4 + [VP]),
+    "tq_cross_entropy": (I, [VP, VP, VP, C.c_int64, VP, VP, I, I, VP]),
+    "tq_classifier_head_bwd": (I, [VP] * 15 + [SZ] + [I] * 4 + [VP]),
 }
 
 def lib_path() -> str:

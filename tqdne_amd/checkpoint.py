@@ -30,12 +30,14 @@ _MODULE_MAP = {
     "tqdne.consistency_model": "tqdne_amd.consistency_model",
     "tqdne.autoencoder": "tqdne_amd.autoencoder",
     "tqdne.unet": "tqdne_amd.unet",
+    "tqdne.classifier": "tqdne_amd.classifier",
 }
 
 
 # classes of the mapped modules a checkpoint may instantiate (hyper_parameters hold a pickled tqdne.edm.EDM; the reference
 # allow-lists exactly that class with add_safe_globals, experiments/generate.py:117-120)
-_MAPPED_CLASSES = {"EDM", "LightningEDM", "LithningConsistencyModel", "LightningAutoencoder", "UNetModel", "Encoder", "Decoder"}
+_MAPPED_CLASSES = {"EDM", "LightningEDM", "LithningConsistencyModel", "LightningAutoencoder", "UNetModel", "Encoder", "Decoder",
+                   "LithningClassifier"}
 
 # everything else a Lightning checkpoint of the reference is made of: tensor / storage rebuild helpers, dtypes, containers,
 # numpy scalars.  A global outside this list is refused: unpickling never runs code a downloaded .ckpt chooses.
@@ -52,6 +54,8 @@ _SAFE_GLOBALS = {
     ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"), ("numpy", "dtype"),
     ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"), ("numpy", "ndarray"),
     ("pathlib", "PosixPath"), ("pathlib", "PurePosixPath"),
+    # the loss module among a classifier's hyper-parameters (classifier.py:46-49; its class weights are an ordinary tensor)
+    ("torch.nn.modules.loss", "CrossEntropyLoss"),
 }
 _SAFE_TORCH_NAMES = {n for n in dir(torch) if n.endswith("Storage")} | {
     n for n in dir(torch) if isinstance(getattr(torch, n, None), torch.dtype)}
@@ -74,7 +78,7 @@ class _RemapUnpickler(pickle.Unpickler):
         if module == "tqdne" or module.startswith("tqdne."):
             raise pickle.UnpicklingError(f"checkpoint references {module}.{name}, which has no tqdne_amd counterpart")
         ok = ((module, name) in _SAFE_GLOBALS or (module, name) in self.extra
-              or (module == "torch" and name in _SAFE_TORCH_NAMES) or (module == "builtins" and name in _SAFE_BUILTINS))
+              or (module == "torch" and name in _SAFE_TORCH_NAMES) or (module in ("builtins", "__builtin__") and name in _SAFE_BUILTINS))   # (__builtin__: protocol 2's spelling of builtins)
         if not ok:
             raise pickle.UnpicklingError(
                 f"refusing to unpickle global {module}.{name} from a checkpoint (not on the allow-list; pass "

@@ -1302,8 +1302,12 @@ class SeqEngine(UNetEngine):
             self.head_btc = self._conv([h], self._site("output_layer", out), stats=False)
             self.head_rec = self.last_rec
 
-    def forward(self, x, train: bool = False, dropout_seed: int = 0):
+    def forward(self, x, train: bool = False, dropout_seed: int = 0, channels_last: bool = False):
+        """``channels_last`` (an output layer wider than 16 channels only): return the output conv's own (B, T', C) buffer,
+        ``head_btc.buf``, and skip the layout flip into the NCW buffer -- for a consumer that reads channels-last (the classifier head)."""
         m, B, T = self.m, self.B, self.T
+        if channels_last and self.out_mode != "conv":
+            raise ValueError("channels_last needs an output layer of more than 16 channels (the generic conv, which writes channels-last)")
         if tuple(x.shape) != (B, m.in_channels, T):
             raise ValueError(f"plan was built for {(B, m.in_channels, T)}, got {tuple(x.shape)}")
         x = x.contiguous()
@@ -1316,14 +1320,23 @@ class SeqEngine(UNetEngine):
         self._run_stem(x, None, m.input_layer, m.in_channels, stream, trace, "input layer", "input layer")
         self._run_ops(self.ops, stream, trace)
         self._fwd_count += 1
+        if channels_last:
+            self._mark_use(stream)
+            return self.head_btc.buf
         self._run_head(m.output_layer, None, stream, trace, "output layer", "output layer")
         self._mark_use(stream)
         return self.out_nct
 
-    def backward(self, dout: torch.Tensor, want_dx: bool = False, clone: bool = True):
-        """Gradients of every parameter of the Encoder / Decoder for d loss / d output = ``dout`` (B, C_out, T_out), for the
-        last forward; with ``want_dx`` also d loss / d input (B, C_in, T).  Returns (list aligned with parameters(), dx|None)."""
+    def backward_plan(self):
+        """The backward plan (built on first use).  A caller that forms d loss / d output channels-last writes it into the plan's
+        ``dout_btc`` (B, T_out, C_out) and then calls ``backward(None)``."""
         from .engine_bwd import SeqBackwardPlan
         if self._bwd is None:
             self._bwd = SeqBackwardPlan(self)
-        return self._bwd.run_seq(dout, want_dx=want_dx, clone=clone)
+        return self._bwd
+
+    def backward(self, dout, want_dx: bool = False, clone: bool = True):
+        """Gradients of every parameter of the Encoder / Decoder for d loss / d output = ``dout`` (B, C_out, T_out), for the
+        last forward; with ``want_dx`` also d loss / d input (B, C_in, T).  Returns (list aligned with parameters(), dx|None).
+        ``dout=None``: the gradient already stands, channels-last, in ``backward_plan().dout_btc``."""
+        return self.backward_plan().run_seq(dout, want_dx=want_dx, clone=clone)

@@ -900,21 +900,26 @@ class SeqBackwardPlan(BackwardPlan):
         # (an input layer of more than 16 channels already ran as the generic conv: its padded channels-last input is the forward's)
         self._stem_gradients(m.input_layer, True, "wgrad:input_layer")
 
-    def run_seq(self, dout: torch.Tensor, want_dx: bool = False, clone: bool = True):
+    def run_seq(self, dout, want_dx: bool = False, clone: bool = True):
+        """``dout`` (B, C_out, T_out), or None: the caller has written d loss / d output channels-last into ``self.dout_btc``."""
         m = self.m
+        if dout is None and self.dout_btc is None:
+            raise ValueError("dout=None needs an output layer of more than 16 channels (a plan with a channels-last gradient buffer)")
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         last = self._begin_run(stream)
         stem = m.input_layer
         cin = stem.in_channels
-        dout = dout.contiguous()
         if not self.wide_stem:
             self.stem_x_btc[:, :, :cin].copy_(last["x"].permute(0, 2, 1))
-        if self.head_op is not None:
+        if dout is None:
+            pass
+        elif self.head_op is not None:
+            dout = dout.contiguous()
             fn, args, what = self.head_op
             args[0] = dout.data_ptr()
             check(fn(*args, stream), what)
         else:
-            self.dout_btc.copy_(dout.permute(0, 2, 1))
+            self.dout_btc.copy_(dout.contiguous().permute(0, 2, 1))
         self._sweep(stream)   # (every launch on the one stream)
         self.gv(stem.weight).copy_(self.dw_stem32[:, :cin, :])
         dx = self._input_gradient(stem, stream, "input_layer") if want_dx else None
