@@ -260,6 +260,41 @@ int tq_conv1d_bwd_weight_colsum(const TqConvDesc* desc, const float* dy, const f
                                 const float* gshift, float* dw, void* workspace, size_t ws_bytes, float* colsum_bc, int bc_stride,
                                 float* colsum_c, float* colsum_c2, hipStream_t stream);
 
+/* How a weight-gradient launch of `desc` is tiled and split (additive at ABI 8; needs no launch -- the slots of the split come from the
+ * device's occupancy where there is one and from the MI355X figures otherwise).  Filled by the functions the launch and
+ * tq_conv1d_bwd_weight_workspace plan with, so a test can name the kernel form and the split regime a case runs in.
+ *   form             TQ_WGRAD_*: the kernel form.  Four waves and a 128-output-channel tile with input chunks of 32 (C32: k = 3 / 5, and
+ *                    k = 1 sources that are not whole 64-channel chunks), 64 (C64: k = 1, 64 | C_in0, C_in1) or 128 channels (C128:
+ *                    k = 1, stride 1, 128 | C_in0, C_in1); W8: eight waves on a 64-channel input tile (k = 3 / 5, 64 | C_in0, C_in1,
+ *                    128 | C_out); H64: four waves on a 64-output-channel tile (k = 3 / 5, stride 1, no upsampling, 64 | C_in0, C_in1,
+ *                    C_out == 64).  A launch that carries fused column sums (with_colsum != 0: colsum_bc or colsum_c given) never takes
+ *                    W8 / H64.
+ *   n_cotiles        output-channel tiles (of 128 channels; 64 in H64), the last one may be partial
+ *   n_cichunks       input-channel chunks of the form's width over C_in0 + C_in1
+ *   n_ttiles         64-position units per sample, ceil(T_out / 64)
+ *   n_units          B * n_ttiles: the (b, t) reduction in units
+ *   n_splits         slabs of the workspace = workgroups per (output tile, input chunk); split s reduces the units
+ *                    [s * units_per_split, min(n_units, (s + 1) * units_per_split)), so the last one may be shorter
+ *   units_per_split  units of a full split
+ *   xcd_order        1: workgroups are numbered so that the input-chunk workgroups of one (split, output tile) pair share an XCD
+ *                    (8 | n_splits * n_cotiles, and TQDNE_WGRAD_XCD=0 not set); 0: the plain order
+ * The grid is n_splits * n_cotiles * n_cichunks workgroups; the workspace of a launch is n_splits * ktaps * C_out * (C_in0 + C_in1)
+ * floats, and tq_conv1d_bwd_weight_workspace is the larger of the with_colsum = 0 / 1 figures.
+ * NULL desc / out: TQ_ERR_ARG; a shape the launch refuses (channels not multiples of 32, ktaps outside {1, 3, 5}, stride 2 with
+ * ktaps != 3, upsampling with ktaps 1) or B, T_in, T_out < 1: TQ_ERR_SHAPE, *out untouched. */
+#define TQ_WGRAD_C32 0
+#define TQ_WGRAD_C64 1
+#define TQ_WGRAD_C128 2
+#define TQ_WGRAD_W8 3
+#define TQ_WGRAD_H64 4
+typedef struct TqWgradPlan {
+    int32_t form;
+    int32_t n_cotiles, n_cichunks, n_ttiles;
+    int32_t n_units, n_splits, units_per_split;
+    int32_t xcd_order;
+} TqWgradPlan;
+int tq_conv1d_bwd_weight_plan(const TqConvDesc* desc, int with_colsum, TqWgradPlan* out);
+
 /* First conv of the network: (B, C_in<=16, T) fp32 input (this kernel's limit; the plans route stems of 17 ... 64 signal channels
  * through tq_nct_to_btc + tq_conv1d_fwd, see the boundary section below), scaled per sample by in_scale[b] (EDM c_in, edm.py:107;
  * NULL = 1), k taps "same" -> (B, T, C_out) channels-last + bias (+ partial statistics (B, ceil(T / 128), C_out, 2)).  unet.py:233.

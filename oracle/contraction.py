@@ -268,6 +268,75 @@ def dgrad_exact(dy, w):
     return conv1d_exact(dy, transposed_weights(w))
 
 
+# ------------------------------------------------------------------------------------------------ weight gradient
+def _wgrad_taps(xhat, T_out, K, stride, upsample):
+    """the K row-shifted views of the staged activation that meet dy[b, t]: xhat (B, T_in, C) -> list of (B, T_out, C);
+    stride 1: source position t + k - K // 2 of the (nearest-x2 upsampled) image, stride 2 (K = 3): 2 t + k - 1; zeros outside"""
+    assert stride in (1, 2) and not (stride == 2 and (upsample or K != 3))
+    src = np.repeat(xhat, 2, axis=1) if upsample else xhat
+    B, T_src, C = src.shape
+    pad = K // 2 if stride == 1 else 1
+    need = (T_out - 1) * stride + K
+    xp = np.zeros((B, max(need, pad + T_src), C), src.dtype)
+    xp[:, pad:pad + T_src] = src
+    return [xp[:, k:k + (T_out - 1) * stride + 1:stride] for k in range(K)]
+
+
+def wgrad_exact(dy, xhat, K, stride=1, upsample=False):
+    """Weight gradient dw (C_out, C_in, K) float64 of a conv with output gradient dy (B, T_out, C_out) and STAGED activation xhat
+    (B, T_in, C_in) (channels-last; after the launch's prologue: GroupNorm fold, SiLU, dropout), summed in float64"""
+    dy, xhat = np.asarray(dy, np.float64), np.asarray(xhat, np.float64)
+    B, T_out, Co = dy.shape
+    a = dy.reshape(B * T_out, Co)
+    taps = _wgrad_taps(xhat, T_out, K, stride, upsample)
+    return np.stack([a.T @ x.reshape(B * T_out, -1) for x in taps], axis=-1)
+
+
+WGRAD_PRODUCTS = ("lo_hi", "hi_lo", "hi_hi")    # (dy part, xhat part) of mfma_x3's three products, in its order
+
+
+def wgrad_products(dy, xhat, K, stride=1, upsample=False):
+    """The three products of mfma_x3 in wgrad_kernel, each (C_out, C_in, K) float64 with exact products and float64 sums, keyed by
+    WGRAD_PRODUCTS: both operands are split with split_bf16 (RNE / RNE, common.hpp) into hi + lo; "lo_hi" = dy_lo xhat_hi, "hi_lo" =
+    dy_hi xhat_lo, "hi_hi" = dy_hi xhat_hi (lo lo is not formed)."""
+    dy, xhat = _f32(dy), _f32(xhat)
+    B, T_out, Co = dy.shape
+    dh, dl = (p.astype(np.float64).reshape(B * T_out, Co) for p in split_bf16(dy))
+    xh, xl = split_bf16(xhat)
+    th = [x.reshape(B * T_out, -1) for x in _wgrad_taps(xh.astype(np.float64), T_out, K, stride, upsample)]
+    tl = [x.reshape(B * T_out, -1) for x in _wgrad_taps(xl.astype(np.float64), T_out, K, stride, upsample)]
+    return {"lo_hi": np.stack([dl.T @ t for t in th], axis=-1), "hi_lo": np.stack([dh.T @ t for t in tl], axis=-1),
+            "hi_hi": np.stack([dh.T @ t for t in th], axis=-1)}
+
+
+def wgrad_model(dy, xhat, K, stride=1, upsample=False, leave_out=None, products=None):
+    """wgrad_exact as wgrad_kernel forms it: the sum of wgrad_products.  ``leave_out``: one of the cross products ("lo_hi" / "hi_lo")
+    is dropped -- only for sizing a test's bar against the error such a defect would make.  ``products``: a wgrad_products result of
+    the same operands, to form several variants without repeating the contractions."""
+    assert leave_out in (None, "lo_hi", "hi_lo")
+    p = products if products is not None else wgrad_products(dy, xhat, K, stride, upsample)
+    return sum(p[n] for n in WGRAD_PRODUCTS if n != leave_out)
+
+
+def wgrad_channel_err(dw, ref):
+    """channel_err of a weight gradient (C_out, C_in, K): per OUTPUT channel (the first axis), the worst one"""
+    return channel_err(np.moveaxis(np.asarray(dw, np.float64), 0, -1), np.moveaxis(np.asarray(ref, np.float64), 0, -1))
+
+
+def staged_dropout(xhat, seed, site, p):
+    """the dropout stage of a prologue on the staged activation xhat (B, T, C) fp32: kept values times 1 / (1 - p) in fp32, element
+    index t * C + c (oracle/dropout.py)"""
+    from .dropout import dropout_scale_mask
+    xhat = _f32(xhat)
+    B, T, C = xhat.shape
+    return (xhat * dropout_scale_mask(seed, site, B, T, C, p)).astype(np.float32)
+
+
+def staged_gn(x, a, s):
+    """a x + s in fp32 as a GroupNorm-only prologue stages it (one fused multiply-add).  x (B, T, C), a / s (B, C)"""
+    return (np.asarray(x, np.float64) * np.asarray(a, np.float64)[:, None, :] + np.asarray(s, np.float64)[:, None, :]).astype(np.float32)
+
+
 def staged_gn_silu(x, a, s):
     """silu(a x + s) in fp32 as a GN + SiLU launch stages it: one fused multiply-add, then u / (1 + exp(-u)).  x (B, T, C), a / s (B, C)"""
     u = (np.asarray(x, np.float64) * np.asarray(a, np.float64)[:, None, :] + np.asarray(s, np.float64)[:, None, :]).astype(np.float32)

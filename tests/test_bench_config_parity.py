@@ -179,43 +179,7 @@ def test_range_guard_moves_the_plan_to_bf16x3():
 
 
 # ---------------------------------------------------------------------------------------------------------------- (iv)
-def _mix32(x):
-    """csrc/common.hpp mix32 on numpy uint32 arrays (wrapping arithmetic)"""
-    M = np.uint32
-    x = np.asarray(x, dtype=np.uint32).copy()
-    with np.errstate(over="ignore"):
-        x ^= x >> M(16)
-        x *= M(0x7FEB352D)
-        x ^= x >> M(15)
-        x *= M(0x846CA68B)
-        x ^= x >> M(16)
-    return x
-
-
-def _drop_key(seed, site, b):
-    """csrc/common.hpp drop_key: the per-sample key of dropout site ``site`` under the 64-bit ``seed``"""
-    M = np.uint32
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    with np.errstate(over="ignore"):
-        k = _mix32(M(seed & 0xFFFFFFFF) ^ M(0x9E3779B9))
-        k = _mix32(k ^ M(seed >> 32))
-        k = _mix32(k + M(0x85EBCA6B) * M(site + 1))
-        return _mix32(k + M(0xC2B2AE35) * M(b + 1)), _mix32((k ^ M(0x27D4EB2F)) + M(0x165667B1) * M(b + 1))
-
-
-def _drop_hash(key, e):
-    """csrc/common.hpp drop_hash: the finaliser with the key's second word added between its two multiplies"""
-    M = np.uint32
-    ka, kb = key
-    x = np.asarray(e, dtype=np.uint32) ^ ka
-    with np.errstate(over="ignore"):
-        x ^= x >> M(16)
-        x *= M(0x7FEB352D)
-        x += kb
-        x ^= x >> M(15)
-        x *= M(0x846CA68B)
-        x ^= x >> M(16)
-    return x
+from oracle.dropout import drop_hash as _drop_hash, drop_key as _drop_key   # (the numpy restatement of csrc/common.hpp lives with the oracle)
 
 
 def _dropout_masks(cfg, B, T_of_block, seed, p):

@@ -110,6 +110,15 @@ class TqConvDesc(C.Structure):
     ]
 
 
+TQ_WGRAD_C32, TQ_WGRAD_C64, TQ_WGRAD_C128, TQ_WGRAD_W8, TQ_WGRAD_H64 = 0, 1, 2, 3, 4    # TqWgradPlan.form
+WGRAD_FORM_NAME = {TQ_WGRAD_C32: "C32", TQ_WGRAD_C64: "C64", TQ_WGRAD_C128: "C128", TQ_WGRAD_W8: "W8", TQ_WGRAD_H64: "H64"}
+
+
+class TqWgradPlan(C.Structure):
+    _fields_ = [("form", C.c_int32), ("n_cotiles", C.c_int32), ("n_cichunks", C.c_int32), ("n_ttiles", C.c_int32),
+                ("n_units", C.c_int32), ("n_splits", C.c_int32), ("units_per_split", C.c_int32), ("xcd_order", C.c_int32)]
+
+
 class TqAdamChunk(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
                 ("n", C.c_int32), ("reserved", C.c_int32)]
@@ -202,6 +211,7 @@ _PROTOS = {
     "tq_conv1d_bwd_weight_workspace": (SZ, [VP]),
     "tq_conv1d_bwd_weight": (I, [VP] * 8 + [SZ, VP]),
     "tq_conv1d_bwd_weight_colsum": (I, [VP] * 8 + [SZ, VP, I, VP, VP, VP]),
+    "tq_conv1d_bwd_weight_plan": (I, [VP, I, VP]),
     "tq_gn_bwd_finalize": (I, [VP, VP, VP, I, I, I, VP, VP, VP, VP, VP, VP]),
     "tq_gn_bwd_apply": (I, [VP] * 7 + [I] * 6 + [VP]),
     "tq_gn_bwd_apply_colsum": (I, [VP] * 7 + [I] * 6 + [VP, I, VP, VP, VP, VP]),

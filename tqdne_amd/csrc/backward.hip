@@ -55,6 +55,9 @@ struct WgArgs {
 
 constexpr int WG_TT = 64;        // reduction positions per staged tile
 constexpr int TQ_WGRAD_PLAIN_ORDER = 1 << 30;  // (internal flag bit of WgArgs.flags: A/B switch TQDNE_WGRAD_XCD=0)
+// The XCD block order (see wgrad_kernel) needs whole groups of 8 (split, co-tile) pairs; asked by the kernel and by the host's plan query
+// (a macro, so that the kernel's branch compiles exactly as the expression written in place)
+#define WG_XCD_ORDER(npairs, flags) (((npairs) & 7) == 0 && !((flags) & TQ_WGRAD_PLAIN_ORDER))
 // LDS images of the weight gradient, conflict-free for ds_read_b64_tr_b16 (32-lane groups: rows {r .. r+3} and {r+8 .. r+11},
 // 8 bytes per lane): row stride = 8 banks (mod 64) for dy, 16 banks for the 64-byte xhat rows, and the 8-byte column slot is
 // XOR-ed with bit 3 of the row (dy: slot ^ 16, xhat: slot ^ 4), so that the two 4-row halves of a group -- 8 rows apart, i.e. a
@@ -122,7 +125,7 @@ __global__ __launch_bounds__((W8 && !H64) ? 512 : 256, (W8 && !H64) ? 1 : 2) voi
     {
         const int bid = blockIdx.x;
         const int npairs = p.nsplit * p.n_cotiles;
-        if ((npairs & 7) == 0 && !(p.flags & TQ_WGRAD_PLAIN_ORDER)) {
+        if (WG_XCD_ORDER(npairs, p.flags)) {
             const int xcd = bid & 7, j = bid >> 3;
             const int pi = (j / p.n_cichunks) * 8 + xcd;
             cc = j % p.n_cichunks;
@@ -552,18 +555,47 @@ int wgrad_slots(const TqConvDesc* d, int nci, bool w8, bool h64) {
     return wgrad_slots_k<1, 1, 0>(nci, false);
 }
 
+// The form decision, in one place (plan, workspace, launch and tq_conv1d_bwd_weight_plan all ask here): H64, else W8 (they exclude each
+// other: C_out == 64 vs 128 | C_out), else the four-wave kernel of 128 output channels with wgrad_nci's chunk.
 // ``wide``: the forms with a 64-channel xhat tile shared by two groups of waves (W8, H64) are allowed; the fused column sums are not
 // built into them, so a launch that carries column sums plans -- and runs -- the four-wave kernel of 128 output channels
-void wgrad_plan(const TqConvDesc* d, bool wide, int& n_cotiles, int& n_cichunks, int& n_ttiles, int& nsplit, int& ups) {
-    const int nci = wgrad_nci(d);
-    const bool h64 = wide && wgrad_h64(d);
-    const bool w8 = wide && (h64 || wgrad_w8(d));
-    n_cotiles = h64 ? 1 : (d->C_out + 127) / 128;
-    n_cichunks = (d->C_in0 + d->C_in1) / (32 * (w8 ? 2 : nci));
+struct WgForm {
+    int form;     // TQ_WGRAD_*
+    int nci;      // four-wave forms: input chunk in units of 32 channels (1, 2, 4)
+    bool w8, h64;
+    bool tile64() const { return w8 || h64; }              // the 64-channel xhat tile shared by two groups of waves
+    int chunk32() const { return tile64() ? 2 : nci; }     // input channels of a workgroup in units of 32
+};
+
+WgForm wgrad_form(const TqConvDesc* d, bool wide) {
+    WgForm f;
+    f.nci = wgrad_nci(d);
+    f.h64 = wide && wgrad_h64(d);
+    f.w8 = wide && !f.h64 && wgrad_w8(d);
+    f.form = f.h64 ? TQ_WGRAD_H64 : f.w8 ? TQ_WGRAD_W8 : f.nci == 4 ? TQ_WGRAD_C128 : f.nci == 2 ? TQ_WGRAD_C64 : TQ_WGRAD_C32;
+    return f;
+}
+
+// Shapes the weight gradient is built for (the launch's and the plan query's argument check)
+int wgrad_check_shape(const TqConvDesc* d) {
+    if (d->C_in0 <= 0 || d->C_in0 % 32 || d->C_in1 < 0 || d->C_in1 % 32 || d->C_out <= 0 || d->C_out % 32) return TQ_ERR_SHAPE;
+    if (d->stride == 2) return d->ktaps == 3 ? 0 : TQ_ERR_SHAPE;
+    if (d->upsample) return (d->ktaps == 5 || d->ktaps == 3) ? 0 : TQ_ERR_SHAPE;
+    return (d->ktaps == 5 || d->ktaps == 3 || d->ktaps == 1) ? 0 : TQ_ERR_SHAPE;
+}
+
+bool wgrad_plain_order() {
+    static const bool plain_order = [] { const char* e = getenv("TQDNE_WGRAD_XCD"); return e && atoi(e) == 0; }();
+    return plain_order;
+}
+
+void wgrad_plan(const TqConvDesc* d, const WgForm& f, int& n_cotiles, int& n_cichunks, int& n_ttiles, int& nsplit, int& ups) {
+    n_cotiles = f.h64 ? 1 : (d->C_out + 127) / 128;
+    n_cichunks = (d->C_in0 + d->C_in1) / (32 * f.chunk32());
     n_ttiles = (d->T_out + WG_TT - 1) / WG_TT;
     const int U = d->B * n_ttiles;
     const int ntiles = n_cotiles * n_cichunks;
-    const int slots = wgrad_slots(d, nci, w8, h64);
+    const int slots = wgrad_slots(d, f.nci, f.tile64(), f.h64);
     int want = slots / ntiles;   // splits per output tile: the grid fills one round of resident workgroups, not more
     if (want < 1) want = 1;
     if (want > U) want = U;
@@ -612,8 +644,8 @@ int launch_wgrad(const WgArgs& a, int nci, bool w8, bool h64, hipStream_t stream
 extern "C" size_t tq_conv1d_bwd_weight_workspace(const TqConvDesc* d) {
     if (!d) return 0;
     int a, b, c, nsplit, nsplit4, ups;   // (the larger of the two plans: with and without fused column sums)
-    wgrad_plan(d, true, a, b, c, nsplit, ups);
-    wgrad_plan(d, false, a, b, c, nsplit4, ups);
+    wgrad_plan(d, wgrad_form(d, true), a, b, c, nsplit, ups);
+    wgrad_plan(d, wgrad_form(d, false), a, b, c, nsplit4, ups);
     return (size_t)(nsplit > nsplit4 ? nsplit : nsplit4) * d->ktaps * d->C_out * (d->C_in0 + d->C_in1) * sizeof(float);
 }
 
@@ -629,7 +661,7 @@ extern "C" int tq_conv1d_bwd_weight_colsum(const TqConvDesc* d, const float* dy,
                                            hipStream_t stream) {
     if (!d || !dy || !x0 || !dw || !workspace) return TQ_ERR_ARG;
     if (colsum_c2 && !colsum_c) return TQ_ERR_ARG;
-    if (d->C_in0 <= 0 || d->C_in0 % 32 || d->C_in1 < 0 || d->C_in1 % 32 || d->C_out <= 0 || d->C_out % 32) return TQ_ERR_SHAPE;
+    if (wgrad_check_shape(d)) return TQ_ERR_SHAPE;
     if (d->C_in1 > 0 && !x1) return TQ_ERR_ARG;
     if ((d->flags & TQ_CONV_GN) && (!gscale || !gshift)) return TQ_ERR_ARG;
     if (ws_bytes < tq_conv1d_bwd_weight_workspace(d)) return TQ_ERR_ARG;
@@ -639,30 +671,24 @@ extern "C" int tq_conv1d_bwd_weight_colsum(const TqConvDesc* d, const float* dy,
     a.flags = d->flags;
     a.cs_bc = colsum_bc; a.cs_stride = bc_stride; a.cs_c = colsum_c; a.cs_c2 = colsum_c2;
     const bool wide = !(colsum_bc || colsum_c);   // (the fused column sums live in the four-wave kernel of 128 output channels)
-    wgrad_plan(d, wide, a.n_cotiles, a.n_cichunks, a.n_ttiles, a.nsplit, a.units_per_split);
-    static const bool plain_order = [] { const char* e = getenv("TQDNE_WGRAD_XCD"); return e && atoi(e) == 0; }();
-    if (plain_order) a.flags |= TQ_WGRAD_PLAIN_ORDER;
+    const WgForm f = wgrad_form(d, wide);
+    wgrad_plan(d, f, a.n_cotiles, a.n_cichunks, a.n_ttiles, a.nsplit, a.units_per_split);
+    if (wgrad_plain_order()) a.flags |= TQ_WGRAD_PLAIN_ORDER;
     a.drop_site = d->dropout_site; a.drop_seed = d->dropout_seed;
     float pdrop = d->dropout_p;
     if (!(d->flags & TQ_CONV_DROPOUT) || pdrop <= 0.f) { a.flags &= ~TQ_CONV_DROPOUT; pdrop = 0.f; }
     a.drop_thresh = (uint32_t)((double)pdrop * 4294967296.0);
     a.drop_scale = 1.0f / (1.0f - pdrop);
     int rc;
-    const int nci = wgrad_nci(d);
-    const bool h64 = wide && wgrad_h64(d);
-    const bool w8 = wide && !h64 && wgrad_w8(d);
     if (d->stride == 2) {
-        if (d->ktaps != 3) return TQ_ERR_SHAPE;
-        rc = launch_wgrad<3, 2, 0>(a, nci, w8, false, stream);
+        rc = launch_wgrad<3, 2, 0>(a, f.nci, f.w8, false, stream);
     } else if (d->upsample) {
-        if (d->ktaps == 5) rc = launch_wgrad<5, 1, 1>(a, nci, w8, false, stream);
-        else if (d->ktaps == 3) rc = launch_wgrad<3, 1, 1>(a, nci, w8, false, stream);
-        else return TQ_ERR_SHAPE;
+        if (d->ktaps == 5) rc = launch_wgrad<5, 1, 1>(a, f.nci, f.w8, false, stream);
+        else rc = launch_wgrad<3, 1, 1>(a, f.nci, f.w8, false, stream);
     } else {
-        if (d->ktaps == 5) rc = launch_wgrad<5, 1, 0>(a, nci, w8, h64, stream);
-        else if (d->ktaps == 3) rc = launch_wgrad<3, 1, 0>(a, nci, w8, h64, stream);
-        else if (d->ktaps == 1) rc = launch_wgrad<1, 1, 0>(a, nci, false, false, stream);
-        else return TQ_ERR_SHAPE;
+        if (d->ktaps == 5) rc = launch_wgrad<5, 1, 0>(a, f.nci, f.w8, f.h64, stream);
+        else if (d->ktaps == 3) rc = launch_wgrad<3, 1, 0>(a, f.nci, f.w8, f.h64, stream);
+        else rc = launch_wgrad<1, 1, 0>(a, f.nci, false, false, stream);
     }
     if (rc) return rc;
     const size_t n = (size_t)d->C_out * (d->C_in0 + d->C_in1);
@@ -671,6 +697,19 @@ extern "C" int tq_conv1d_bwd_weight_colsum(const TqConvDesc* d, const float* dy,
     else if (d->ktaps == 3) hipLaunchKernelGGL(wgrad_reduce_kernel<3>, rgrid, rblock, 0, stream, a.slab, dw, a.nsplit, n);
     else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, rgrid, rblock, 0, stream, a.slab, dw, a.nsplit, n);
     TQ_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int tq_conv1d_bwd_weight_plan(const TqConvDesc* d, int with_colsum, TqWgradPlan* out) {
+    if (!d || !out) return TQ_ERR_ARG;
+    if (wgrad_check_shape(d) || d->B < 1 || d->T_in < 1 || d->T_out < 1) return TQ_ERR_SHAPE;
+    const WgForm f = wgrad_form(d, !with_colsum);
+    TqWgradPlan p;
+    p.form = f.form;
+    wgrad_plan(d, f, p.n_cotiles, p.n_cichunks, p.n_ttiles, p.n_splits, p.units_per_split);
+    p.n_units = d->B * p.n_ttiles;
+    p.xcd_order = WG_XCD_ORDER(p.n_splits * p.n_cotiles, wgrad_plain_order() ? TQ_WGRAD_PLAIN_ORDER : 0) ? 1 : 0;
+    *out = p;
     return 0;
 }
 

@@ -272,18 +272,42 @@ def conv1d_bwd_data(dy, weight, *, x0=None, x1=None, gscale=None, gshift=None, s
     return g0, g1, st
 
 
+def wgrad_desc(B, T_in, T_out, C0, C1, C_out, K, stride=1, upsample=False, flags=0):
+    """TqConvDesc of a weight-gradient launch (what conv1d_bwd_weight, conv1d_bwd_weight_plan and the workspace query are given)"""
+    d = TqConvDesc()
+    d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, T_in, T_out, C0, C1, C_out
+    d.ktaps, d.stride, d.pad, d.upsample = K, stride, K // 2, int(upsample)
+    d.flags = flags
+    return d
+
+
+def conv1d_bwd_weight_plan(desc, with_colsum=False):
+    """How the weight gradient of ``desc`` (wgrad_desc) is tiled and split: the TqWgradPlan of tq_conv1d_bwd_weight_plan as a dict, plus
+    ``form_name``, ``last_split`` (units of the last split), ``workspace_bytes`` of this launch's slabs, and ``crosses_sample`` (some
+    split holds units of two samples).  Launches nothing and needs no device."""
+    lib = _lib.load()
+    p = _lib.TqWgradPlan()
+    check(lib.tq_conv1d_bwd_weight_plan(C.byref(desc), int(bool(with_colsum)), C.byref(p)), "conv1d_bwd_weight_plan")
+    out = {n: getattr(p, n) for n, _ in p._fields_}
+    ups, U, nt = p.units_per_split, p.n_units, p.n_ttiles
+    out["form_name"] = _lib.WGRAD_FORM_NAME[p.form]
+    out["last_split"] = U - (p.n_splits - 1) * ups
+    out["workspace_bytes"] = p.n_splits * desc.ktaps * desc.C_out * (desc.C_in0 + desc.C_in1) * 4
+    out["crosses_sample"] = any(s * ups // nt != (min(U, (s + 1) * ups) - 1) // nt for s in range(p.n_splits))
+    return out
+
+
 def conv1d_bwd_weight(dy, x0, wshape, *, x1=None, gscale=None, gshift=None, silu=False, stride=1, upsample=False,
-                      dropout_p=0.0, dropout_seed=0, dropout_site=0, colsum=None, out=None):
-    """weight gradient; ``colsum`` = (per-sample sums (B, C_out) | None, per-channel sums (C_out,) | None): column sums of dy ACCUMULATED
-    into those tensors by the same launch (tq_conv1d_bwd_weight_colsum)"""
+                      dropout_p=0.0, dropout_seed=0, dropout_site=0, colsum=None, out=None, workspace=None):
+    """weight gradient; ``colsum`` = (per-sample sums (B, C_out) | None, per-channel sums (C_out,) | None[, second destination of the
+    per-channel sums (C_out,) | None]): column sums of dy ACCUMULATED into those tensors by the same launch
+    (tq_conv1d_bwd_weight_colsum).  ``workspace``: caller-owned uint8 buffer for the slabs (its numel is passed as the byte count;
+    default: a fresh one of tq_conv1d_bwd_weight_workspace bytes)."""
     lib = _lib.load()
     B, T_in, C0 = x0.shape
     C1 = 0 if x1 is None else x1.shape[2]
     C_out, C_in, K = wshape
     T_out = dy.shape[1]
-    d = TqConvDesc()
-    d.B, d.T_in, d.T_out, d.C_in0, d.C_in1, d.C_out = B, T_in, T_out, C0, C1, C_out
-    d.ktaps, d.stride, d.pad, d.upsample = K, stride, K // 2, int(upsample)
     f = 0
     if gscale is not None:
         f |= TQ_CONV_GN
@@ -291,14 +315,17 @@ def conv1d_bwd_weight(dy, x0, wshape, *, x1=None, gscale=None, gshift=None, silu
         f |= TQ_CONV_SILU
     if dropout_p > 0:
         f |= TQ_CONV_DROPOUT
-    d.flags = f
+    d = wgrad_desc(B, T_in, T_out, C0, C1, C_out, K, stride, upsample, f)
     d.dropout_site, d.dropout_p, d.dropout_seed = dropout_site, dropout_p, dropout_seed
-    ws = torch.empty(lib.tq_conv1d_bwd_weight_workspace(C.byref(d)), dtype=torch.uint8, device=dy.device)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(lib.tq_conv1d_bwd_weight_workspace(C.byref(d)), dtype=torch.uint8, device=dy.device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
     dw = torch.empty(C_out, C_in, K, device=dy.device) if out is None else out   # (``out``: caller-owned (C_out, C_in, K) buffer)
     if colsum is not None:
-        bc, c1 = colsum
+        bc, c1, c2 = colsum if len(colsum) == 3 else (*colsum, None)
         check(lib.tq_conv1d_bwd_weight_colsum(C.byref(d), _p(dy), _p(x0), _p(x1), _p(gscale), _p(gshift), _p(dw), _p(ws), ws.numel(),
-                                              _p(bc), C_out if bc is not None else 0, _p(c1), None, _stream(dy.device)),
+                                              _p(bc), C_out if bc is not None else 0, _p(c1), _p(c2), _stream(dy.device)),
               "conv1d_bwd_weight_colsum")
         return dw
     check(lib.tq_conv1d_bwd_weight(C.byref(d), _p(dy), _p(x0), _p(x1), _p(gscale), _p(gshift), _p(dw), _p(ws), ws.numel(),
