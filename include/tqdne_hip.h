@@ -685,6 +685,37 @@ int tq_classifier_head_bwd(const float* dlogits, const float* pooled, const floa
                            const float* W2, const float* W3, float* dW3, float* db3, float* dW2, float* db2, float* dW1, float* db1,
                            float* dh, void* workspace, size_t workspace_bytes, int B, int T, int C, int K, hipStream_t stream);
 
+/* ---- LogSpectrogram (csrc/spectrogram.hip; added under ABI 8; representation.py:63-175) ------------------------- */
+/* The STFT of librosa.stft(y, n_fft, hop_length) at its defaults (win_length = n_fft, periodic Hann, center=True with n_fft / 2
+ * zeros on either side, F = 1 + T / hop frames) and librosa.griffinlim(S, n_iter, hop_length, n_fft, momentum, init="random",
+ * random_state) in one launch.  Exact fp32 arithmetic (FMA, logf / expf / hypotf, true division; no fast-math functions, no
+ * atomics): every sum has an order that depends on (n_fft, hop, F) alone, so results are bit-reproducible and a waveform's result
+ * does not depend on the rest of the batch.  Built for n_fft = 256 with hop 32 or 64; the Nyquist row is never stored (the
+ * reference drops it after the STFT and feeds zeros for it to the inversion).
+ *   tables: a device copy of what tq_spectrogram_tables wrote -- Hann window, cos and sin of 2 pi m / n_fft (n_fft floats each) and,
+ *     for F > 0, the window sum-square of F frames (hop (F - 1) + n_fft floats), all computed in double.  A table made for F frames
+ *     serves tq_stft_fwd for any length and tq_griffinlim for exactly F frames.  tq_spectrogram_table_floats: its length (0 for
+ *     arguments the kernels refuse).  Both are host functions and touch no device.
+ *   tq_stft_fwd: x (N, T) -> either or both of spec (N, n_fft / 2, F) as interleaved (re, im) fp32 and repr (N, n_fft / 2, F) =
+ *     2 (log max(|S|, clip) - log clip) / (log_max - log clip) - 1, in one launch.  Any T >= n_fft.
+ *   tq_griffinlim: in (N, n_fft / 2, F) -> out (N, hop (F - 1)).  `in` holds magnitudes, or with log_input != 0 the normalised
+ *     log-magnitudes above, mapped back by exp((r + 1) / 2 (log_max - log clip) + log clip) as they are loaded.  phase: (n_fft / 2, F)
+ *     interleaved (cos, sin) of the initial phases, shared by all N waveforms (the reference draws
+ *     RandomState(0).random((n_fft / 2 + 1, F)) for every waveform).  Each of the n_iter iterations: y = istft(A), R = stft(y),
+ *     C = R - momentum / (1 + momentum) * Rprev (no such term in the first), A = S C / (|C| + FLT_MIN); the result is istft(A).
+ *     One workgroup per waveform holds all state on chip; F <= tq_griffinlim_max_frames(n_fft, hop) = 128.
+ * Argument checks, before the device is touched: NULL x / in / out / tables / phase, neither spec nor repr, n_iter < 0, a
+ * non-positive n_fft or hop, a hop that does not divide n_fft, or (where the log map is used) clip <= 0 or log_max <= log clip:
+ * TQ_ERR_ARG; an n_fft / hop without a kernel, N < 1, T < n_fft (hop (F - 1) < n_fft) or F above the limit: TQ_ERR_SHAPE.  The
+ * limit query returns the same codes for the same n_fft / hop. */
+int tq_griffinlim_max_frames(int n_fft, int hop);
+size_t tq_spectrogram_table_floats(int n_fft, int hop, int F);
+int tq_spectrogram_tables(int n_fft, int hop, int F, float* host_out);
+int tq_stft_fwd(const float* x, float* spec, float* repr, const float* tables, int N, int T, int n_fft, int hop, double clip,
+                double log_max, hipStream_t stream);
+int tq_griffinlim(const float* in, float* out, const float* tables, const float* phase, int N, int F, int n_fft, int hop, int n_iter,
+                  double momentum, int log_input, double clip, double log_max, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

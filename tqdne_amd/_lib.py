@@ -241,6 +241,11 @@ _PROTOS = {
     "tq_classifier_head_fwd": (I, [VP] * 11 + [I] * 4 + [VP]),
     "tq_cross_entropy": (I, [VP, VP, VP, C.c_int64, VP, VP, I, I, VP]),
     "tq_classifier_head_bwd": (I, [VP] * 15 + [SZ] + [I] * 4 + [VP]),
+    "tq_griffinlim_max_frames": (I, [I, I]),
+    "tq_spectrogram_table_floats": (SZ, [I, I, I]),
+    "tq_spectrogram_tables": (I, [I, I, I, VP]),
+    "tq_stft_fwd": (I, [VP] * 4 + [I] * 4 + [C.c_double] * 2 + [VP]),
+    "tq_griffinlim": (I, [VP] * 4 + [I] * 5 + [C.c_double, I, C.c_double, C.c_double, VP]),
 }
 
 def lib_path() -> str:
