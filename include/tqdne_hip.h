@@ -716,6 +716,26 @@ int tq_stft_fwd(const float* x, float* spec, float* repr, const float* tables, i
 int tq_griffinlim(const float* in, float* out, const float* tables, const float* phase, int N, int F, int n_fft, int hop, int n_iter,
                   double momentum, int log_input, double clip, double log_max, hipStream_t stream);
 
+/* ---- ground-motion intensity measures (csrc/intensity.hip; added under ABI 8; scripts/seismo_evaluations) ---------- */
+/* Directional peaks of N two-component waveforms, the input of GMRotDpp / RotDpp (smtk's semantics restated):
+ *     peaks[n, k, phi] = max_t | sx_k(t) cos phi + sy_k(t) sin phi |,   phi = 0 .. 179 degrees (0 and 90 exactly unrotated),
+ * over the T - 1 samples of K = 3 + P series pairs: k = 0 the ground acceleration x[:-1], k = 1 its velocity
+ * dt * cumulative_trapezoid(a, initial 0), k = 2 the displacement (the same of v), k = 3 + i the absolute acceleration
+ * -(2 xi w u' + w^2 u) of the oscillator u'' + 2 xi w u' + w^2 u = -a(t), w = 2 pi / periods[i], from rest, a linear between
+ * samples, solved exactly from sample to sample (Nigam-Jennings; output sample j is the state at (j + 1) dt).
+ *   tables: a device copy of what tq_oscillator_tables wrote (tq_oscillator_table_floats(P) = 360 + 12 P floats): cos and sin of
+ *     the 180 angles, then per period the step of the scaled state s = (w^2 u, w u'), s' = A s + B0 a_j + B1 a_(j+1), as
+ *     A11 A12 A21 A22 B0[0] B0[1] B1[0] B1[1] 2xi 0 0 0, all computed in double.  Host functions; they touch no device.
+ *   tq_rotd_peaks: x, y (N, T) -> peaks (N, 3 + P, 180), one launch, no atomics, no workspace; any T >= 2 (there is no limit on
+ *     T).  Every sum has one order that depends on (T, P) alone: launches repeat bit for bit and a waveform's values do not depend
+ *     on the rest of the batch.  A waveform with a non-finite sample in either component gets NaN in all of its values.
+ * Argument checks, before the device is touched: NULL pointers, P < 0, dt not positive and finite, damping outside [0, 1), a period
+ * not positive and finite: TQ_ERR_ARG; N < 1 or T < 2: TQ_ERR_SHAPE. */
+size_t tq_oscillator_table_floats(int P);
+int tq_oscillator_tables(const double* periods, int P, double dt, double damping, float* host_out);
+int tq_rotd_peaks(const float* x, const float* y, const float* tables, float* peaks, int N, int T, int P, double dt,
+                  hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

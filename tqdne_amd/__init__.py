@@ -19,6 +19,7 @@ from .unet import UNetModel
 from .classifier import LithningClassifier
 from .metric import (AmplitudeSpectralDensity, FrechetInceptionDistance, InceptionScore, MeanSquaredError, Metric, NeuralMetric,
                      frechet_distance)
+from .ground_motion import gmrotdpp_with_pg, parallel_processing_sa, response_spectrum, rotd_peaks
 
 __version__ = "0.1.0"
 __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler", "LithningConsistencyModel", "LightningAutoencoder", "Encoder", "Decoder", "get_1d_unet_config",
@@ -26,3 +27,4 @@ __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler",
            "tiny_1d_unet_config"]
 __all__ += ["LithningClassifier", "frechet_distance", "Metric", "MeanSquaredError", "AmplitudeSpectralDensity", "NeuralMetric",
             "FrechetInceptionDistance", "InceptionScore"]
+__all__ += ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa"]

@@ -13,7 +13,7 @@ LIBPATH = os.path.join(LIBDIR, "libtqdne_hip.so")
 # (the conv kernel template, csrc/conv1d_kernel.hpp, is instantiated by seven translation units so that the build runs in parallel)
 SOURCES = ["conv1d_fwd_k5a.hip", "conv1d_fwd_k5b.hip", "conv1d_fwd_k13.hip", "conv1d_resample.hip", "conv1d_dgrad.hip", "conv1d_mfma.hip",
            "conv1d_fwd_wide.hip", "conv1d_fwd_wide_k13.hip", "small_ops.hip", "attention.hip", "attention_hd.hip", "backward.hip", "ends_wide.hip", "boundary.hip",
-           "resample_plain.hip", "classifier.hip", "spectrogram.hip"]
+           "resample_plain.hip", "classifier.hip", "spectrogram.hip", "intensity.hip"]
 ARCH = "gfx950"
 
 

@@ -246,6 +246,9 @@ _PROTOS = {
     "tq_spectrogram_tables": (I, [I, I, I, VP]),
     "tq_stft_fwd": (I, [VP] * 4 + [I] * 4 + [C.c_double] * 2 + [VP]),
     "tq_griffinlim": (I, [VP] * 4 + [I] * 5 + [C.c_double, I, C.c_double, C.c_double, VP]),
+    "tq_oscillator_table_floats": (SZ, [I]),
+    "tq_oscillator_tables": (I, [VP, I, C.c_double, C.c_double, VP]),
+    "tq_rotd_peaks": (I, [VP] * 4 + [I] * 3 + [C.c_double, VP]),
 }
 
 def lib_path() -> str:
