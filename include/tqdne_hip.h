@@ -25,7 +25,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define TQ_ABI_VERSION 8
+#define TQ_ABI_VERSION 9
 
 #define TQ_ERR_ARG (-1)   /* null / inconsistent pointer arguments */
 #define TQ_ERR_SHAPE (-2) /* unsupported shape */
@@ -167,8 +167,6 @@ typedef struct TqConvBwdDesc {
 } TqConvBwdDesc;
 
 int tq_abi_version(void);
-/* Bit mask of optional parts compiled into this library: there are none, always 0 (kept for ABI 5 callers). */
-int tq_build_flags(void);
 
 /* ---- weights -------------------------------------------------------------------------------------------- */
 /* Pack a torch Conv1d weight (C_out, C_in, K) fp32 into per-lane MFMA fragments.
@@ -326,7 +324,7 @@ int tq_head_conv_fwd(const float* x, const float* gscale, const float* gshift, c
 int tq_gn_finalize(const float* stats0, int C0, const float* stats1, int C1, int B, int T, const float* gamma,
                    const float* beta, float* gscale, float* gshift, float* mean_rstd, int slot0, int slot1, hipStream_t stream);
 
-/* GroupNorm32 backward, step 1: per-channel partial sums {sum g, sum g*x} (from tq_conv1d_bwd_data / tq_head_conv_bwd)
+/* GroupNorm32 backward, step 1: per-channel partial sums {sum g, sum g*x} (from tq_conv1d_bwd_data / tq_head_conv_bwd_ws)
  * + saved mean/rstd + gamma -> coefficients with dx = A*g + Bc*x + Cc, and dgamma/dbeta (atomically added: zero them first). */
 int tq_gn_bwd_finalize(const float* gstats_partial, const float* mean_rstd, const float* gamma, int B, int C, int T,
                        float* coef_a, float* coef_b, float* coef_c, float* dgamma, float* dbeta, hipStream_t stream);
@@ -383,32 +381,28 @@ int tq_pair_sum(const float* d_up, float* dx, int B, int T, int C, int accumulat
  * k = 3 conv): folds dw2 (2 C_out, C_in, 3) = [d even-phase taps | d odd-phase taps] back onto the conv's five taps, dw (C_out, C_in, 5)
  * (overwritten): dw0 = dA0 + dB0, dw1 = dA0 + dB1, dw2 = dA1 + dB1, dw3 = dA1 + dB2, dw4 = dA2 + dB2. */
 int tq_upsample_poly_wgrad_fold(const float* dw2, float* dw, int C_out, int C_in, hipStream_t stream);
-/* stem conv weight gradient (atomically added into zeroed dw (C_out, C_in, K)).  Keeps its limit of C_out C_in K <= 2048 weights
- * (TQ_ERR_SHAPE beyond): the plans form the gradient of a wider stem with tq_conv1d_bwd_weight on a 32-channel channels-last copy of
- * the input (bf16x3 error bars), whatever the first-level width. */
-int tq_stem_conv_bwd_weight(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in, int T,
-                            int C_out, int ktaps, hipStream_t stream);
-/* ABI 5: the same two with a scratch buffer of tq_stem_head_bwd_workspace() bytes (own buffer per call site and stream): every
- * workgroup's 960 partial sums go to its row of the scratch and a second small launch adds the rows into dw (db) -- the outputs share
- * 30 cache lines, and atomics on one LINE serialise at ~11 ns each (512 workgroups: 180 us, the whole time of these kernels).
- * workspace NULL or too small: the atomic form.  dw / db are still ADDED to (zero them first). */
+/* Backward of the stem and head convs.  Both ADD into dw (and db): zero them first.
+ * workspace: tq_stem_head_bwd_workspace() bytes of scratch (own buffer per call site and stream): every workgroup's partial sums go
+ * to its row of the scratch and a second small launch adds the rows into dw (db) -- the outputs share 30 cache lines, and atomics on
+ * one LINE serialise at ~11 ns each (512 workgroups: 180 us, the whole time of these kernels).  workspace NULL or too small: the
+ * workgroups add into dw (db) with atomics instead. */
 size_t tq_stem_head_bwd_workspace(void);
+/* stem conv weight gradient dw (C_out, C_in, K).  Keeps its limit of C_out C_in K <= 2048 weights (TQ_ERR_SHAPE beyond): the plans
+ * form the gradient of a wider stem with tq_conv1d_bwd_weight on a 32-channel channels-last copy of the input (bf16x3 error bars),
+ * whatever the first-level width. */
 int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in, int T,
                                int C_out, int ktaps, void* workspace, size_t ws_bytes, hipStream_t stream);
+/* head conv backward: dF = c_out[b]*dpred; g_out (B,T,C_in) = (W^T*dF)*silu'(gscale*x+gshift) with GN partial sums
+ * {sum g, sum g x} per channel and 128-position slot; dw, db as above.
+ * C_in: the powers of two 8 ... 256 (first kernels, unchanged) and every multiple of 32 up to 1024 (csrc/ends_wide.hip: a grid
+ * dimension over chunks of <= 128 input channels, exact fp32 like the first kernels); C_out <= 16; k in {1, 3, 5}.  The fixed
+ * tq_stem_head_bwd_workspace() bytes serve every such shape: the chunked kernel launches no more workgroups per chunk than partial
+ * rows of C_out C_in k + 16 floats fit the workspace it is given (25 at 1024 x 16 x 5). */
+/* LDS bytes tq_head_conv_bwd_ws needs for a shape; 0 = unsupported shape.  Needs no device. */
+size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps);
 int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, const float* x, const float* gscale, const float* gshift,
                         const float* w, float* g_out, float* gstats_partial, float* dw, float* db, int B, int T, int C_in,
                         int C_out, int ktaps, void* workspace, size_t ws_bytes, hipStream_t stream);
-/* head conv backward: dF = c_out[b]*dpred; g_out (B,T,C_in) = (W^T*dF)*silu'(gscale*x+gshift) with GN partial sums
- * {sum g, sum g x} per channel and 128-position slot; dw, db atomically added (zero them first).
- * C_in: the powers of two 8 ... 256 (first kernels, unchanged) and every multiple of 32 up to 1024 (csrc/ends_wide.hip: a grid
- * dimension over chunks of <= 128 input channels, exact fp32 like the first kernels); C_out <= 16; k in {1, 3, 5}.  The _ws form
- * with the fixed tq_stem_head_bwd_workspace() bytes serves every such shape: the chunked kernel launches no more workgroups per
- * chunk than partial rows of C_out C_in k + 16 floats fit the workspace it is given (25 at 1024 x 16 x 5). */
-/* LDS bytes tq_head_conv_bwd(_ws) needs for a shape; 0 = unsupported shape.  Needs no device. */
-size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps);
-int tq_head_conv_bwd(const float* dpred_nct, const float* c_out, const float* x, const float* gscale, const float* gshift,
-                     const float* w, float* g_out, float* gstats_partial, float* dw, float* db, int B, int T, int C_in,
-                     int C_out, int ktaps, hipStream_t stream);
 
 /* ---- embeddings ------------------------------------------------------------------------------------------- */
 /* emb = time_mlp(fourier(t)) (+ cond_mlp(cond)); writes emb (B, E) and silu(emb) (B, E).  E = 4*mc.
@@ -431,29 +425,27 @@ size_t tq_attention_workspace_bytes(int B, int T, int H, int D);
 int tq_attention_fwd(const float* qkv, float* out, float* lse /* (B,H,T) log-sum-exp per query, NULL at inference */,
                      void* workspace /* tq_attention_workspace_bytes(); NULL selects the workspace-free kernel */, int B, int T,
                      int H, int D, hipStream_t stream);
-/* backward of the above (recomputes P from qkv and lse): dqkv (B, T, 3*H*D) from dout (B, T, H*D);
- * delta (B,H,T) is scratch.  Two passes: queries-stationary for dq, keys-stationary for dk/dv (no atomics). */
 /* attention core on q from qkv and K / V planes already written by tq_conv1d_fwd_qkv (no log-sum-exp output: inference) */
 int tq_attention_fwd_presplit(const float* qkv, const void* kv_planes, float* out, int B, int T, int H, int D, int v_format,
                               hipStream_t stream);
-int tq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv, int B,
-                     int T, int H, int D, hipStream_t stream);
-/* the same with a scratch buffer of 2 * tq_attention_workspace_bytes(): second-generation kernels for D = 32 / 64 (one prep pass
- * writes bf16 hi / lo planes of Q, K, V, dO and delta; both passes then stream 16-byte copies, P / dS stay in registers); D = 128 or
- * workspace == NULL fall through to tq_attention_bwd.  Replaces the autograd backward of blocks.py:156-190. */
+/* Backward of tq_attention_fwd (recomputes P from qkv and lse): dqkv (B, T, 3*H*D) from dout (B, T, H*D); delta (B,H,T) is scratch.
+ * Replaces the autograd backward of blocks.py:156-190.  workspace: 2 * tq_attention_workspace_bytes() of scratch, nullable.  With it,
+ * D = 32 / 64 run the second-generation kernels (one prep pass writes bf16 hi / lo planes of Q, K, V, dO and delta; both passes then
+ * stream 16-byte copies, P / dS stay in registers).  D = 128, or workspace == NULL, run the first-generation kernels: two passes,
+ * queries-stationary for dq, keys-stationary for dk/dv (no atomics). */
 int tq_attention_bwd_ws(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                         void* workspace, int B, int T, int H, int D, hipStream_t stream);
-/* ABI 6.  The same with the K / V planes the training forward already wrote: `kv_planes` is the `workspace` argument of the
+/* The same with the K / V planes the training forward already wrote: `kv_planes` is the `workspace` argument of the
  * tq_attention_fwd call whose backward this is (D = 32 / 64; it must still hold that call's planes: give every attention block of a
  * training plan a workspace of its own).  The prep pass then forms Q, dO and delta only.  `workspace`: as tq_attention_bwd_ws
  * (its first half stays unused).  Gradients bit-identical to tq_attention_bwd_ws. */
 int tq_attention_bwd_ws_kv(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                            void* workspace, const void* kv_planes, int B, int T, int H, int D, hipStream_t stream);
 
-/* ABI 8.  Every head size D with 8 | D and 8 <= D <= 256 (attention_hd.hip): the first-generation kernels (attention_g1.hpp, the text that tq_attention_fwd / tq_attention_bwd instantiate for
+/* ABI 8.  Every head size D with 8 | D and 8 <= D <= 256 (attention_hd.hip): the first-generation kernels (attention_g1.hpp, the text that tq_attention_fwd / tq_attention_bwd_ws instantiate for
  * an exact head size, here instantiated with the padding masks) on the smallest tile in
  * {32, 64, 128, 256} that holds the head; channels >= D are zero-filled on load and skipped on store, strides and the D^-1/4 scale are
- * those of the true D.  Same tensors and layouts as tq_attention_fwd / tq_attention_bwd.  The entry points above keep their contract
+ * those of the true D.  Same tensors and layouts as tq_attention_fwd / tq_attention_bwd_ws.  The entry points above keep their contract
  * (D in {32, 64, 128}, TQ_ERR_SHAPE otherwise).
  *   tq_attention_head_tile: the tile width for head size D, 0 where there is no kernel (needs no device).
  *   tq_attention_hd_lds_bytes: dynamic LDS of a launch, pass 0 forward, 1 dQ, 2 dK / dV; 0 without a kernel (needs no device).
@@ -585,12 +577,11 @@ typedef struct TqAdamChunk {
     int32_t n;
     int32_t reserved;
 } TqAdamChunk;
-int tq_adam_ema_step(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
-                     double inv_bias2_sqrt, double ema_weight, double grad_scale, double decay_factor, hipStream_t stream);
-/* ABI 3: the same update behind a DEVICE-side predicate: when `*skip_flag != 0` at execution time the launch leaves parameters,
- * moments and EMA untouched.  The data-parallel trainer passes the range-guard flag of the fp16-range forward scheme
+/* skip_flag (nullable: NULL = unconditional): a DEVICE-side predicate -- when `*skip_flag != 0` at execution time the launch leaves
+ * parameters, moments and EMA untouched.  The data-parallel trainer passes the range-guard flag of the fp16-range forward scheme
  * (TqConvDesc.range_flag, max-reduced over the ranks): a step whose forward came close to the fp16 range is dropped on the device,
- * without a host synchronisation, before the host has seen the flag and moved the plan to bf16x3.  NULL: unconditional. */
+ * without a host synchronisation, before the host has seen the flag and moved the plan to bf16x3.
+ * NULL table or n_chunks < 0: TQ_ERR_ARG; n_chunks == 0: 0, nothing launched. */
 int tq_adam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
                              double inv_bias2_sqrt, double ema_weight, double grad_scale, double decay_factor,
                              const int32_t* skip_flag, hipStream_t stream);
@@ -631,7 +622,7 @@ int tq_radam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double st
                               double clip_value, hipStream_t stream);
 
 /* The second half of the EMA callback (ema.py:30-48: EMA weights into the module before every validation / test / predict pass, the
- * training weights back afterwards) as an exchange in place, an addition to ABI 8: for every chunk with ema != NULL, p[i] <-> ema[i] for
+ * training weights back afterwards) as an exchange in place: for every chunk with ema != NULL, p[i] <-> ema[i] for
  * i < n.  One launch for the whole model, the optimizer kernel's geometry (one workgroup of 256 threads per chunk, 16-byte body, one-word
  * tail), no second copy of the weights.  Only p, ema and n of a chunk are read (g, m, v may be NULL); chunks whose ema is NULL are left
  * alone.  Bit patterns are moved, nothing is rounded: NaN payloads, infinities, -0.0 and denormals arrive unchanged, and two calls restore

@@ -63,7 +63,7 @@ def test_unsupported_widths_are_refused_at_construction():
 def test_abi_and_limits_without_a_device():
     from tqdne_amd import _lib
     lib = _lib.load()
-    assert lib.tq_abi_version() == 8
+    assert lib.tq_abi_version() == _lib.ABI_VERSION
     new = {"tq_classifier_head_fwd", "tq_classifier_head_bwd", "tq_cross_entropy", "tq_classifier_head_max_channels",
            "tq_classifier_head_max_classes", "tq_classifier_head_bwd_workspace"}
     assert new <= set(_lib.exported_symbols())

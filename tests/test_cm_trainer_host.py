@@ -1,5 +1,5 @@
 """Consistency-model training on the fused path, the part that needs no GPU: the one-launch RAdam entry point is declared, exported
-and bound (ABI unchanged); FusedRAdamEMA's refusals; DataParallelTrainer with a module whose ``configure_optimizers`` returns a BARE
+and bound; FusedRAdamEMA's refusals; DataParallelTrainer with a module whose ``configure_optimizers`` returns a BARE
 optimizer (the reference's consistency model returns ``torch.optim.RAdam(...)``, consistency_model.py:178-190): no scheduler, torch
 RAdam's exact trajectory, ``max_steps=`` published to the module; two gloo ranks against one-rank full-batch training."""
 
@@ -23,14 +23,14 @@ def _free_port():
     return p
 
 
-def test_radam_entry_point_is_declared_exported_and_bound_at_abi_8():
+def test_radam_entry_point_is_declared_exported_and_bound():
     from tqdne_amd import _build, _lib
     _build.build(verbose=False)
     lib = _lib.load()
     header = open(os.path.join(ROOT, "include", "tqdne_hip.h")).read()
     assert re.search(r"\bint\s+tq_radam_ema_step_guarded\s*\(\s*const TqAdamChunk\*", header)
     assert "tq_radam_ema_step_guarded" in _lib.exported_symbols() and hasattr(lib, "tq_radam_ema_step_guarded")
-    assert re.search(r"#define\s+TQ_ABI_VERSION\s+8\b", header) and _lib.ABI_VERSION == 8 and lib.tq_abi_version() == 8
+    assert lib.tq_abi_version() == _lib.ABI_VERSION
     # a null table / an empty one is refused before the device is touched (this box has none)
     args = (1e-3, 0.9, 0.999, 1e-8, 0.0, 0.0, 1.0, None, None)
     assert lib.tq_radam_ema_step_guarded(None, 4, *args) == -1   # TQ_ERR_ARG

@@ -1,5 +1,5 @@
 """Validation and sampling on the EMA weights, checkpoints and resuming -- the part that needs no GPU: ``tq_ema_swap`` is declared,
-exported and bound (an addition to ABI 8: the version stays) and refuses bad arguments before the device is touched;
+exported and bound and refuses bad arguments before the device is touched;
 DataParallelTrainer's ``ema_weights`` / ``validate`` / ``evaluate`` / ``save_checkpoint`` / ``load_checkpoint`` / ``fit`` on the unfused
 path (torch's optimizer on a CPU stub module); ``validate`` over two gloo ranks."""
 

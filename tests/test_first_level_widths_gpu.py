@@ -1,5 +1,5 @@
 """Stem and head convs at every first-level width 32, 64, ... 1024 on the GPU (csrc/ends_wide.hip behind tq_stem_conv_fwd,
-tq_head_conv_fwd, tq_head_conv_bwd[_ws]).
+tq_head_conv_fwd, tq_head_conv_bwd_ws).
 
 Kernel level: the three entry points against fp64 convolutions / fp64 autograd into sentinel-guarded buffers, at widths that are no
 power of two (96, 160, 192, 224, 288, 992), at 512 and 1024 (too wide for one workgroup's LDS), for every tap count and 1 ... 16 signal

@@ -50,7 +50,7 @@ HEAD_LDS_BEFORE = {
 def _queries():
     from tqdne_amd import _lib
     lib = _lib.load()
-    assert lib.tq_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.tq_abi_version() == _lib.ABI_VERSION
     return lib.tq_head_conv_lds_bytes, lib.tq_head_conv_bwd_lds_bytes, lambda c, co, k: lib.tq_stem_conv_lds_bytes(co, c, k)
 
 

@@ -125,7 +125,7 @@ def test_key_split_on_peaked_scores(B, H, D, T):
 @pytest.mark.parametrize("H,D,T", [(2, 32, 190), (4, 64, 512), (1, 64, 127), (1, 128, 512), (2, 128, 100)])
 def test_new_entry_points_equal_the_established_kernels_bit_for_bit(H, D, T):
     """at head sizes 32 / 64 / 128 the padded instantiations (PAD = true) of the first-generation kernels run with every mask true: same
-    arithmetic in the same order as the exact ones (PAD = false; ``workspace=False``: tq_attention_fwd without planes, tq_attention_bwd)"""
+    arithmetic in the same order as the exact ones (PAD = false; ``workspace=False``: tq_attention_fwd / tq_attention_bwd_ws without a workspace)"""
     from tqdne_amd import ops
     g = torch.Generator().manual_seed(H * D + T)
     B = 2

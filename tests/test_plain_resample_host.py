@@ -99,7 +99,7 @@ def test_options_that_stay_refused(fx):
 def test_new_entry_points_check_their_arguments_without_a_gpu():
     from tqdne_amd import _lib
     lib = _lib.load()
-    assert lib.tq_abi_version() == 8
+    assert lib.tq_abi_version() == _lib.ABI_VERSION
     fake = 0x1000   # never dereferenced: every call below is rejected during validation
     for fn in (lib.tq_avg_pool2_fwd, lib.tq_nearest_up2_fwd):
         assert fn(None, fake, fake, 2, 8, 32, None) == -1

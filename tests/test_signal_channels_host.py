@@ -28,7 +28,7 @@ def test_the_limit_query_and_the_abi_number():
     from tqdne_amd import _lib
     lib = _lib.load()
     assert lib.tq_boundary_max_channels() == 64
-    assert lib.tq_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.tq_abi_version() == _lib.ABI_VERSION
     # the dedicated kernels keep their limit: the plans route 17 ... 64 signal channels around them
     assert lib.tq_stem_conv_lds_bytes(17, 32, 5) == 0 and lib.tq_head_conv_lds_bytes(32, 17, 5) == 0
     assert lib.tq_head_conv_bwd_lds_bytes(32, 17, 5) == 0

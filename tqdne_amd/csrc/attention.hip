@@ -824,20 +824,15 @@ int launch_attn_bwd2(const float* qkv, const float* out, const float* d_o, const
     TQ_CHECK_LAUNCH();
     return 0;
 }
-}  // namespace
-
-extern "C" int tq_attention_bwd_ws(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,
-                                   float* dqkv, void* workspace, int B, int T, int H, int D, hipStream_t stream);
-
-extern "C" int tq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,
-                                float* dqkv, int B, int T, int H, int D, hipStream_t stream) {
-    if (!qkv || !out || !dout || !lse || !delta || !dqkv) return TQ_ERR_ARG;
-    if (B <= 0 || T <= 0 || H <= 0) return TQ_ERR_SHAPE;
+// first-generation backward: every D at a NULL workspace, and D = 128 always (arguments checked by tq_attention_bwd_ws)
+int attention_bwd_g1(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv, int B, int T,
+                     int H, int D, hipStream_t stream) {
     if (D == 64) return launch_bwd<64, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
     if (D == 32) return launch_bwd<32, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
     if (D == 128) return launch_bwd<128, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);
     return TQ_ERR_SHAPE;
 }
+}  // namespace
 
 extern "C" int tq_attention_bwd_ws_kv(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,
                                       float* dqkv, void* workspace, const void* kv_planes, int B, int T, int H, int D,
@@ -855,5 +850,5 @@ extern "C" int tq_attention_bwd_ws(const float* qkv, const float* out, const flo
     if (B <= 0 || T <= 0 || H <= 0) return TQ_ERR_SHAPE;
     if (workspace && D == 64) return launch_attn_bwd2<64>(qkv, out, dout, lse, delta, dqkv, workspace, B, T, H, stream);
     if (workspace && D == 32) return launch_attn_bwd2<32>(qkv, out, dout, lse, delta, dqkv, workspace, B, T, H, stream);
-    return tq_attention_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);   // D = 128, or no workspace: first generation
+    return attention_bwd_g1(qkv, out, dout, lse, delta, dqkv, B, T, H, D, stream);   // D = 128, or no workspace
 }

@@ -1643,11 +1643,6 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 constexpr int STEM_HEAD_WGS_MAX = 2048, STEM_WGRAD_WGS = 1024, HEAD_BWD_WGS = 512;
 extern "C" size_t tq_stem_head_bwd_workspace(void) { return (size_t)STEM_HEAD_WGS_MAX * 1024 * sizeof(float); }
 
-extern "C" int tq_stem_conv_bwd_weight(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in,
-                                       int T, int C_out, int ktaps, hipStream_t stream) {
-    return tq_stem_conv_bwd_weight_ws(dy, x_nct, in_scale, dw, B, C_in, T, C_out, ktaps, nullptr, 0, stream);
-}
-
 extern "C" int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, const float* in_scale, float* dw, int B, int C_in,
                                           int T, int C_out, int ktaps, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!dy || !x_nct || !dw) return TQ_ERR_ARG;
@@ -1690,7 +1685,7 @@ extern "C" int tq_stem_conv_bwd_weight_ws(const float* dy, const float* x_nct, c
     return 0;
 }
 
-// dynamic LDS of the kernel tq_head_conv_bwd(_ws) launches for a shape, 0 = not built for it: the launcher's conditions, in its order
+// dynamic LDS of the kernel tq_head_conv_bwd_ws launches for a shape, 0 = not built for it: the launcher's conditions, in its order
 extern "C" size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps) {
     if (ktaps != 1 && ktaps != 3 && ktaps != 5) return 0;
     if (!(C_in < 8 || C_in % 8 || 256 % (C_in / 4) || C_out < 1 || C_out > 16)) {
@@ -1703,12 +1698,6 @@ extern "C" size_t tq_head_conv_bwd_lds_bytes(int C_in, int C_out, int ktaps) {
         if (sh <= 160 * 1024) return sh;
     }
     return ends_wide_head_bwd_lds(C_in, C_out, ktaps);
-}
-
-extern "C" int tq_head_conv_bwd(const float* dpred_nct, const float* c_out, const float* x, const float* gscale,
-                                const float* gshift, const float* w, float* g_out, float* gstats, float* dw, float* db, int B,
-                                int T, int C_in, int C_out, int ktaps, hipStream_t stream) {
-    return tq_head_conv_bwd_ws(dpred_nct, c_out, x, gscale, gshift, w, g_out, gstats, dw, db, B, T, C_in, C_out, ktaps, nullptr, 0, stream);
 }
 
 extern "C" int tq_head_conv_bwd_ws(const float* dpred_nct, const float* c_out, const float* x, const float* gscale,

@@ -10,7 +10,6 @@
 using namespace tq;
 
 extern "C" int tq_abi_version(void) { return TQ_ABI_VERSION; }
-extern "C" int tq_build_flags(void) { return 0; }   // (no optional parts; kept for ABI 5 callers)
 
 // =================================================================================================
 // GroupNorm32 finalisation: per-channel partial (sum, sumsq) of up to two concatenated sources ->
@@ -1230,13 +1229,6 @@ extern "C" int tq_radam_ema_step_guarded(const TqAdamChunk* chunks, int n_chunks
     if (!chunks || n_chunks <= 0) return TQ_ERR_ARG;
     return launch_adam_ema<true>(chunks, n_chunks, step_size, beta1, beta2, eps, rect, ema_weight, grad_scale, 1.0, skip_flag, nullptr,
                                  0.0, stream);
-}
-
-extern "C" int tq_adam_ema_step(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2, double eps,
-                                double inv_bias2_sqrt, double ema_weight, double grad_scale, double decay_factor,
-                                hipStream_t stream) {
-    return tq_adam_ema_step_guarded(chunks, n_chunks, step_size, beta1, beta2, eps, inv_bias2_sqrt, ema_weight, grad_scale,
-                                    decay_factor, nullptr, stream);
 }
 
 extern "C" int tq_adam_ema_step_clipped(const TqAdamChunk* chunks, int n_chunks, double step_size, double beta1, double beta2,

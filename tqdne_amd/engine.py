@@ -323,7 +323,7 @@ def _check_boundary_limits(what: str, name: str, channels: int, k: int):
 
 
 def _check_head_bwd_limits(C_in: int, C_out: int, k: int, name: str = "out.2"):
-    """The same for tq_head_conv_bwd (tq_head_conv_bwd_lds_bytes), asked when a training plan is built."""
+    """The same for tq_head_conv_bwd_ws (tq_head_conv_bwd_lds_bytes), asked when a training plan is built."""
     if _lib.load().tq_head_conv_bwd_lds_bytes(C_in, C_out, k) == 0:
         raise NotImplementedError(
             f"backward of output conv {name}: {C_in} -> {C_out} channels, k = {k}: the HIP head backward kernels take C_in a power of two "
@@ -925,7 +925,7 @@ class UNetEngine:
         ws_bytes = self.lib.tq_attention_hd_workspace_bytes if hd else self.lib.tq_attention_workspace_bytes
         ws = self._attn_workspace(ws_bytes(self.B, x.T, ab.num_heads, D), "_attn_ws_hd" if hd else "_attn_ws")
         # inference forwards: the qkv projection writes K / V as the attention kernel's bf16 hi / lo planes itself (no fp32 K / V,
-        # no split pass: -134 MB and one launch per block); forwards a backward may follow keep fp32 qkv for tq_attention_bwd
+        # no split pass: -134 MB and one launch per block); forwards a backward may follow keep fp32 qkv for tq_attention_bwd_ws
         split = (ws, ab.num_heads, D) if D in (32, 64) else None
         i_qkv = len(self.ops)
         qkv = self._conv([x], self._site(name + ".qkv", ab.qkv), gn=g, silu=False, stats=False, qkv_planes=split, ckpt_tag="qkv")
