@@ -19,7 +19,10 @@ from .unet import UNetModel
 from .classifier import LithningClassifier
 from .metric import (AmplitudeSpectralDensity, FrechetInceptionDistance, InceptionScore, MeanSquaredError, Metric, NeuralMetric,
                      frechet_distance)
-from .ground_motion import gmrotdpp_with_pg, parallel_processing_sa, response_spectrum, rotd_peaks
+from .ground_motion import evaluate_ratio, gmrotdpp_with_pg, parallel_processing_sa, response_spectrum, rotd_peaks
+from . import spectra
+from .spectra import (amplitude_spectrum, column_moments, filter_frequency_domain, integrate_frequency_domain, log_amplitude_spectrum,
+                      rdft, spectral_filter)
 
 __version__ = "0.1.0"
 __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler", "LithningConsistencyModel", "LightningAutoencoder", "Encoder", "Decoder", "get_1d_unet_config",
@@ -27,4 +30,6 @@ __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler",
            "tiny_1d_unet_config"]
 __all__ += ["LithningClassifier", "frechet_distance", "Metric", "MeanSquaredError", "AmplitudeSpectralDensity", "NeuralMetric",
             "FrechetInceptionDistance", "InceptionScore"]
-__all__ += ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa"]
+__all__ += ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa", "evaluate_ratio"]
+__all__ += ["spectra", "rdft", "amplitude_spectrum", "log_amplitude_spectrum", "spectral_filter", "column_moments",
+            "integrate_frequency_domain", "filter_frequency_domain"]

@@ -1,4 +1,5 @@
-"""Build libtqdne_hip.so (hipcc, gfx950 only) in-tree under tqdne_amd/lib/."""
+"""Build libtqdne_hip.so (the model library) and libtqdne_eval.so (the evaluation library, csrc_eval/) with hipcc, gfx950 only,
+in-tree under tqdne_amd/lib/."""
 
 from __future__ import annotations
 
@@ -15,6 +16,10 @@ SOURCES = ["conv1d_fwd_k5a.hip", "conv1d_fwd_k5b.hip", "conv1d_fwd_k13.hip", "co
            "conv1d_fwd_wide.hip", "conv1d_fwd_wide_k13.hip", "small_ops.hip", "attention.hip", "attention_hd.hip", "backward.hip", "ends_wide.hip", "boundary.hip",
            "resample_plain.hip", "classifier.hip", "spectrogram.hip", "intensity.hip"]
 ARCH = "gfx950"
+# the evaluation library (include/tqdne_eval.h): its own sources, its own staleness check, the model library's flags
+CSRC_EVAL = os.path.join(HERE, "csrc_eval")
+EVAL_LIBPATH = os.path.join(LIBDIR, "libtqdne_eval.so")
+EVAL_SOURCES = ["spectra.hip"]
 
 
 def _hipcc() -> str:
@@ -36,17 +41,36 @@ def needs_build(path: str = None) -> bool:
     return any(os.path.getmtime(d) > t for d in _deps() if os.path.exists(d))
 
 
+def _eval_deps():
+    return [os.path.join(CSRC_EVAL, f) for f in os.listdir(CSRC_EVAL)] + [os.path.join(CSRC, "common.hpp"),
+                                                                          os.path.join(HERE, "..", "include", "tqdne_eval.h")]
+
+
+def eval_needs_build() -> bool:
+    if not os.path.exists(EVAL_LIBPATH):
+        return True
+    t = os.path.getmtime(EVAL_LIBPATH)
+    return any(os.path.getmtime(d) > t for d in _eval_deps() if os.path.exists(d))
+
+
 def build(force: bool = False, verbose: bool = True, extra_flags=(), out_name=None) -> str:
-    """Compile every HIP source for gfx950 and link the C-ABI shared library."""
+    """Compile every HIP source for gfx950 and link the C-ABI shared libraries; returns the model library's path.  ``out_name``: an
+    A/B build of the model library alone under that name."""
+    if out_name is None and (force or eval_needs_build()):
+        _compile_and_link(CSRC_EVAL, EVAL_SOURCES, EVAL_LIBPATH, "", verbose, extra_flags)
     global_out = LIBPATH if out_name is None else os.path.join(LIBDIR, out_name)
     if out_name is None and not force and not needs_build(global_out):
         return global_out
-    os.makedirs(LIBDIR, exist_ok=True)
     tag = "" if out_name is None else "." + out_name.replace(".so", "")
+    return _compile_and_link(CSRC, SOURCES, global_out, tag, verbose, extra_flags)
+
+
+def _compile_and_link(csrc, sources, global_out, tag, verbose, extra_flags) -> str:
+    os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES:
-        path = os.path.join(CSRC, src)
+    for src in sources:
+        path = os.path.join(csrc, src)
         if not os.path.exists(path):
             continue
         obj = os.path.join(LIBDIR, src.replace(".hip", tag + ".o"))

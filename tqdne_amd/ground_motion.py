@@ -1,5 +1,6 @@
 """Ground-motion intensity measures of generated waveforms on the GPU (the reference's scripts/seismo_evaluations:
-``gmrotdpp_withPG`` and ``parallel_processing_sa`` of example_GMM.py, ``process_kanno`` of utils.py).
+``gmrotdpp_withPG`` and ``parallel_processing_sa`` of example_GMM.py; ``evaluate_ratio`` of utils.py with its ``calculate_gmrotd50``
+and ``process_kanno`` reductions, on the frequency-domain integration / high-pass of ``spectra.py``).
 
 The reference judges a waveform set against ground-motion models by PGA, PGV, PGD and the 5 %-damped spectral acceleration SA(T),
 each combined over the two horizontal components as GMRotDpp.  It computes them with smtk on ten host processes, one waveform at a
@@ -23,7 +24,8 @@ import torch
 from . import _lib
 from ._lib import check
 
-__all__ = ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa", "N_ANGLES"]
+__all__ = ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa", "calculate_gmrotd50", "process_kanno",
+           "evaluate_ratio", "N_ANGLES"]
 
 N_ANGLES = 180
 _TABLES = {}   # (periods, dt, damping, device) -> device tensor of tq_oscillator_tables
@@ -152,3 +154,44 @@ def response_spectrum(a, dt, periods, damping=0.05):
 def parallel_processing_sa(wf_NS, wf_EW, dt, periods, percentile):
     """The reference's call: GMRotDpp spectral accelerations (N, P) of N waveform pairs (no process pool: one launch)."""
     return gmrotdpp_with_pg(wf_NS, wf_EW, dt, periods, percentile)["Acceleration"]
+
+
+def calculate_gmrotd50(c1, c2):
+    """The reference's ``calculate_gmrotd50`` for batches (..., T) of equal length: max over time of the median over 180 rotation
+    angles of sqrt(r1^2 + r2^2).  The rotation (r1, r2) = (c1 cos + c2 sin, -c1 sin + c2 cos) is orthogonal, so r1^2 + r2^2 =
+    c1^2 + c2^2 at every angle: the median over the angles does not depend on the angle and is sqrt(c1^2 + c2^2) itself."""
+    return torch.sqrt(c1 * c1 + c2 * c2).amax(dim=-1)
+
+
+def process_kanno(EW, NS):
+    """The reference's ``process_kanno`` for batches (..., T): sqrt(max|EW|^2 + max|NS|^2), the two peaks at their own times"""
+    a, b = EW.abs().amax(dim=-1), NS.abs().amax(dim=-1)
+    return torch.sqrt(a * a + b * b)
+
+
+def evaluate_ratio(target, predicted, dt=0.01, n_worker=4, evaluate_obs=True, PGV=True, kanno=False):
+    """The reference's ``evaluate_ratio`` (scripts/seismo_evaluations/utils.py): peak values of observed (``target``) and generated
+    (``predicted``) two-component waveforms (n, 2, T), component 0 = NS, 1 = EW.  ``PGV``: the series are integrated in the frequency
+    domain and reduced by ``calculate_gmrotd50`` (``kanno``: by ``process_kanno``); otherwise they are high-passed and reduced by
+    ``calculate_gmrotd50`` (``kanno`` is not read, as in the reference).  Returns {"PGV_geom_mean_obs", "PGV_geom_mean_gwm"} (or
+    "PGA_..."), each (n,), or the generated set's values alone with ``evaluate_obs=False``.  ``n_worker`` is accepted and ignored: the
+    whole batch is two launches per set, no chunks and no process pool."""
+    from . import spectra
+    for name, a in (("target", target), ("predicted", predicted)):
+        shape = _shape_of(a, name)
+        if len(shape) != 3 or shape[1] < 2:
+            raise ValueError(f"{name}: expected (n, 2, T) waveforms, got {shape}")
+        spectra._check_length(a, name)
+    transform = spectra.integrate_frequency_domain if PGV else spectra.filter_frequency_domain
+    reduce_ = process_kanno if (PGV and kanno) else calculate_gmrotd50
+
+    def peaks(w):
+        wg, kind = spectra._to_gpu(w)
+        s = transform(wg[:, :2], dt)
+        return _back(reduce_(s[:, 1], s[:, 0]), kind)
+
+    gwm = peaks(predicted)
+    if not evaluate_obs:
+        return gwm
+    q = "PGV" if PGV else "PGA"
+    return {f"{q}_geom_mean_obs": peaks(target), f"{q}_geom_mean_gwm": gwm}

@@ -1,6 +1,6 @@
 """Evaluation metrics (third stage of the reference's workflow; counterpart of ``tqdne.metric``, metric.py:13-173): mean squared
-error and amplitude spectral density on the signals themselves, Frechet inception distance and inception score through a trained
-``LithningClassifier``.
+error and amplitude spectral density on the signals themselves (the latter on the GPU for GPU tensors), Frechet inception distance
+and inception score through a trained ``LithningClassifier``.
 
 The embeddings / class probabilities come from the classifier module (on the GPU: the HIP encoder plan and head kernels), in batches of
 ``batch_size``; the statistics are formed on the host in float64 with numpy / scipy by the reference's formulas.  Two departures from
@@ -82,17 +82,38 @@ class MeanSquaredError(Metric):
 
 
 class AmplitudeSpectralDensity(Metric):
-    """Frechet distance between the log amplitude spectra of two sets of signals (``np.fft.rfft`` on the host, as in the reference)."""
+    """Frechet distance between the log amplitude spectra of two sets of signals.  numpy arrays and CPU tensors: ``np.fft.rfft`` on the
+    host, as in the reference.  Two tensors on a GPU: the log spectra are one launch on the channel view (``spectra``, tqe_rdft in LOG
+    mode: no waveform and no spectrum leaves the device); ``isotropic=True`` then takes the float64 column moments and the two sums on
+    the device too, ``isotropic=False`` moves the log spectra to the host for the matrix square root, as FID does."""
 
     def __init__(self, fs, channel=0, log_eps=1e-8, isotropic=True):
         super().__init__(channel)
         self.fs, self.log_eps, self.isotropic = fs, log_eps, isotropic
+
+    def __call__(self, pred, target):
+        if isinstance(pred, th.Tensor) and isinstance(target, th.Tensor) and pred.is_cuda and target.is_cuda:
+            if self.channel is not None:
+                pred, target = pred[:, self.channel], target[:, self.channel]
+            return self.compute_device(pred, target)
+        return super().__call__(pred, target)
 
     def spectral_density(self, signal):
         return np.log(np.clip(np.abs(np.fft.rfft(signal, axis=-1)), self.log_eps, None))
 
     def compute(self, pred, target):
         return frechet_distance(self.spectral_density(pred), self.spectral_density(target), isotropic=self.isotropic)
+
+    def compute_device(self, pred, target):
+        from . import spectra
+        sp, st = (spectra.log_amplitude_spectrum(x.detach(), self.log_eps) for x in (pred, target))
+        if not self.isotropic:
+            return frechet_distance(sp.cpu().numpy().astype(np.float64), st.cpu().numpy().astype(np.float64), isotropic=False)
+        (mu_p, sd_p), (mu_t, sd_t) = (spectra.column_moments(s.reshape(s.shape[0], -1)) for s in (sp, st))
+        d = ((mu_p - mu_t) ** 2).sum() + ((sd_p - sd_t) ** 2).sum()
+        # (the host path's result type for this input type, whatever numpy's promotion rules make it)
+        host_type = self.spectral_density(np.zeros((1, 2), to_numpy(pred.new_zeros(()).cpu()).dtype)).dtype.type
+        return host_type(d.item())
 
 
 class NeuralMetric(Metric):
