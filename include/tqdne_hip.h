@@ -10,6 +10,9 @@
  * Layouts: activations (B, T, C) fp32, C contiguous; network input/output (B, C, T) fp32 as in the reference;
  * per-channel partial statistics (B, nslots, C, 2) fp32 with nslots = ceil(T / 128) and {sum, sum of squares};
  * GroupNorm folded to per-(b, c) scale/shift (B, C) fp32:  norm(x) = scale * x + shift.
+ *   RANGE of the partial statistics: the sums are fp32 and un-shifted ({sum y, sum y^2}; backward {sum g, sum g*x}), combined in fp64, so
+ *   variance and S2 - mean*S1 cancel once a group's mean is far from zero.  Every emitted entry is within (n + 1) 2^-24 sum|terms| of
+ *   the exact sum of its n rows (each producer, tests/test_groupnorm_gpu.py); what that costs downstream is stated at tq_gn_finalize.
  */
 #ifndef TQDNE_HIP_H
 #define TQDNE_HIP_H
@@ -140,7 +143,8 @@ typedef struct TqConvDesc {
 #define TQ_BWD_SILU 2     /* forward applied SiLU: multiply by silu'(gscale*x+gshift) */
 #define TQ_BWD_DROPOUT 4  /* forward applied dropout: re-generate the same mask */
 #define TQ_BWD_ACCUM 8    /* add to dx instead of overwriting (tensor consumed by several ops) */
-#define TQ_BWD_STATS 16   /* emit per-channel partial sums {sum g, sum g*x} for the GroupNorm backward */
+#define TQ_BWD_STATS 16   /* emit per-channel partial sums {sum g, sum g*x} for the GroupNorm backward.  Not together with
+                           * TQ_BWD_ACCUM (TQ_ERR_ARG): the sums would be taken of the accumulated tensor, not of g. */
 
 typedef struct TqConvBwdDesc {
     int32_t B, T;
@@ -321,6 +325,17 @@ int tq_head_conv_fwd(const float* x, const float* gscale, const float* gshift, c
  * emitted by their producers.  Writes scale/shift (B, C0+C1) and mean/rstd (B, 32, 2).  nn.py:11-13,90-105. */
 /* slot0 / slot1 (ABI 5): positions per statistics slot of each source -- 128 (0 = default) or 32 (a tensor written by a
  * TqConvDesc.t_tile = 32 launch); stats_i is (B, ceil(T / slot_i), C_i, 2). */
+/* RANGE (measured on the kernels, tests/test_groupnorm_gpu.py::test_chain_under_mean_std_regimes; worst of four shapes and two
+ * producers; max|error| / max|float64| per tensor; in parentheses a CPU emulation of fp32 slot sums taken sequentially, the least
+ * accurate order, on the same inputs).  By |group mean| / group std of the normalised tensor:
+ *     ratio   scale*x + shift       dx (whole backward chain)   dgamma
+ *       0     8.1e-8 (1.9e-7)       1.2e-7 (2.1e-7)             1.2e-7 (2.8e-7)
+ *       3     1.5e-6 (3.6e-6)       2.1e-6 (3.2e-6)             1.7e-6 (2.4e-6)
+ *      10     1.8e-5 (5.3e-5)       1.2e-5 (3.7e-5)             1.7e-5 (3.0e-5)
+ *      30     1.3e-4 (3.1e-4)       1.4e-4 (2.7e-4)             9.4e-5 (5.4e-4)
+ *     100     1.5e-3 (3.2e-3)       1.2e-3 (3.2e-3)             1.2e-3 (2.7e-3)
+ * i.e. ~ratio^2 * 2^-24 * 2: inside 1e-3 up to a ratio of 30, beyond it around 100 (dbeta is a plain sum: 1.3e-7 throughout).  A group
+ * with sum y^2 / n <= mean^2 (constant, or statistics that do not belong together) gets variance 0: rstd = 1 / sqrt(eps). */
 int tq_gn_finalize(const float* stats0, int C0, const float* stats1, int C1, int B, int T, const float* gamma,
                    const float* beta, float* gscale, float* gshift, float* mean_rstd, int slot0, int slot1, hipStream_t stream);
 

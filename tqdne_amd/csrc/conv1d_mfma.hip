@@ -152,6 +152,8 @@ extern "C" int tq_conv1d_bwd_data(const TqConvBwdDesc* d, const float* dy, const
     if (need_x && (!x0 || (d->C_dx1 > 0 && !x1))) return TQ_ERR_ARG;
     if ((d->flags & TQ_BWD_GN) && (!gscale || !gshift)) return TQ_ERR_ARG;
     if ((d->flags & TQ_BWD_STATS) && !gstats) return TQ_ERR_ARG;
+    // (the epilogue would sum the tensor AFTER accumulation: {sum (g + old), sum (g + old) x}, the GroupNorm backward sums of nothing)
+    if ((d->flags & TQ_BWD_ACCUM) && (d->flags & TQ_BWD_STATS)) return TQ_ERR_ARG;
     if (d->B <= 0 || d->T <= 0 || (d->ktaps != 1 && d->ktaps != 3 && d->ktaps != 5)) return TQ_ERR_SHAPE;
     ConvArgs a;
     a.x0 = dy; a.x1 = nullptr; a.gscale = nullptr; a.gshift = nullptr;
