@@ -23,6 +23,9 @@ from .ground_motion import evaluate_ratio, gmrotdpp_with_pg, parallel_processing
 from . import spectra
 from .spectra import (amplitude_spectrum, column_moments, filter_frequency_domain, integrate_frequency_domain, log_amplitude_spectrum,
                       rdft, spectral_filter)
+from . import conditioning
+from .conditioning import (bandpass, butter_sos, condition_stream, detrend, highpass_filter, moving_average_envelope_adaptive,
+                           sosfilt)
 
 __version__ = "0.1.0"
 __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler", "LithningConsistencyModel", "LightningAutoencoder", "Encoder", "Decoder", "get_1d_unet_config",
@@ -33,3 +36,5 @@ __all__ += ["LithningClassifier", "frechet_distance", "Metric", "MeanSquaredErro
 __all__ += ["rotd_peaks", "gmrotdpp_with_pg", "response_spectrum", "parallel_processing_sa", "evaluate_ratio"]
 __all__ += ["spectra", "rdft", "amplitude_spectrum", "log_amplitude_spectrum", "spectral_filter", "column_moments",
             "integrate_frequency_domain", "filter_frequency_domain"]
+__all__ += ["conditioning", "sosfilt", "butter_sos", "highpass_filter", "bandpass", "detrend", "condition_stream",
+            "moving_average_envelope_adaptive"]

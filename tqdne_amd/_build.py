@@ -1,5 +1,5 @@
-"""Build libtqdne_hip.so (the model library) and libtqdne_eval.so (the evaluation library, csrc_eval/) with hipcc, gfx950 only,
-in-tree under tqdne_amd/lib/."""
+"""Build libtqdne_hip.so (the model library), libtqdne_eval.so (the evaluation library, csrc_eval/) and libtqdne_series.so (the
+conditioning library, csrc_series/) with hipcc, gfx950 only, in-tree under tqdne_amd/lib/."""
 
 from __future__ import annotations
 
@@ -20,6 +20,10 @@ ARCH = "gfx950"
 CSRC_EVAL = os.path.join(HERE, "csrc_eval")
 EVAL_LIBPATH = os.path.join(LIBDIR, "libtqdne_eval.so")
 EVAL_SOURCES = ["spectra.hip"]
+# the conditioning library (include/tqdne_series.h), built the same way
+CSRC_SERIES = os.path.join(HERE, "csrc_series")
+SERIES_LIBPATH = os.path.join(LIBDIR, "libtqdne_series.so")
+SERIES_SOURCES = ["series.hip"]
 
 
 def _hipcc() -> str:
@@ -53,11 +57,25 @@ def eval_needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in _eval_deps() if os.path.exists(d))
 
 
+def _series_deps():
+    return [os.path.join(CSRC_SERIES, f) for f in os.listdir(CSRC_SERIES)] + [os.path.join(CSRC, "common.hpp"),
+                                                                              os.path.join(HERE, "..", "include", "tqdne_series.h")]
+
+
+def series_needs_build() -> bool:
+    if not os.path.exists(SERIES_LIBPATH):
+        return True
+    t = os.path.getmtime(SERIES_LIBPATH)
+    return any(os.path.getmtime(d) > t for d in _series_deps() if os.path.exists(d))
+
+
 def build(force: bool = False, verbose: bool = True, extra_flags=(), out_name=None) -> str:
     """Compile every HIP source for gfx950 and link the C-ABI shared libraries; returns the model library's path.  ``out_name``: an
     A/B build of the model library alone under that name."""
     if out_name is None and (force or eval_needs_build()):
         _compile_and_link(CSRC_EVAL, EVAL_SOURCES, EVAL_LIBPATH, "", verbose, extra_flags)
+    if out_name is None and (force or series_needs_build()):
+        _compile_and_link(CSRC_SERIES, SERIES_SOURCES, SERIES_LIBPATH, "", verbose, extra_flags)
     global_out = LIBPATH if out_name is None else os.path.join(LIBDIR, out_name)
     if out_name is None and not force and not needs_build(global_out):
         return global_out
