@@ -26,6 +26,9 @@ from .spectra import (amplitude_spectrum, column_moments, filter_frequency_domai
 from . import conditioning
 from .conditioning import (bandpass, butter_sos, condition_stream, detrend, highpass_filter, moving_average_envelope_adaptive,
                            sosfilt)
+from . import duration
+from .duration import (calculate_arias_intensity, calculate_resultant_horizontal, calculate_signal_duration, compute_time_derivative,
+                       husid, shaking_duration, significant_duration)
 
 __version__ = "0.1.0"
 __all__ = ["UNetModel", "EDM", "LightningEDM", "LightningDDMP", "DDPMScheduler", "LithningConsistencyModel", "LightningAutoencoder", "Encoder", "Decoder", "get_1d_unet_config",
@@ -38,3 +41,5 @@ __all__ += ["spectra", "rdft", "amplitude_spectrum", "log_amplitude_spectrum", "
             "integrate_frequency_domain", "filter_frequency_domain"]
 __all__ += ["conditioning", "sosfilt", "butter_sos", "highpass_filter", "bandpass", "detrend", "condition_stream",
             "moving_average_envelope_adaptive"]
+__all__ += ["duration", "compute_time_derivative", "calculate_resultant_horizontal", "calculate_arias_intensity",
+            "calculate_signal_duration", "significant_duration", "husid", "shaking_duration"]

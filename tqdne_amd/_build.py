@@ -1,5 +1,6 @@
 """Build libtqdne_hip.so (the model library), libtqdne_eval.so (the evaluation library, csrc_eval/) and libtqdne_series.so (the
-conditioning library, csrc_series/) with hipcc, gfx950 only, in-tree under tqdne_amd/lib/."""
+conditioning library, csrc_series/) with hipcc, gfx950 only, in-tree under tqdne_amd/lib/.
+libtqdne_duration.so (the Arias-intensity / duration library, csrc_duration/) is the fourth, built the same way."""
 
 from __future__ import annotations
 
@@ -24,6 +25,10 @@ EVAL_SOURCES = ["spectra.hip"]
 CSRC_SERIES = os.path.join(HERE, "csrc_series")
 SERIES_LIBPATH = os.path.join(LIBDIR, "libtqdne_series.so")
 SERIES_SOURCES = ["series.hip"]
+# the duration library (include/tqdne_duration.h), built the same way
+CSRC_DURATION = os.path.join(HERE, "csrc_duration")
+DURATION_LIBPATH = os.path.join(LIBDIR, "libtqdne_duration.so")
+DURATION_SOURCES = ["duration.hip"]
 
 
 def _hipcc() -> str:
@@ -69,6 +74,18 @@ def series_needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in _series_deps() if os.path.exists(d))
 
 
+def _duration_deps():
+    return [os.path.join(CSRC_DURATION, f) for f in os.listdir(CSRC_DURATION)] + [os.path.join(CSRC, "common.hpp"),
+                                                                                  os.path.join(HERE, "..", "include", "tqdne_duration.h")]
+
+
+def duration_needs_build() -> bool:
+    if not os.path.exists(DURATION_LIBPATH):
+        return True
+    t = os.path.getmtime(DURATION_LIBPATH)
+    return any(os.path.getmtime(d) > t for d in _duration_deps() if os.path.exists(d))
+
+
 def build(force: bool = False, verbose: bool = True, extra_flags=(), out_name=None) -> str:
     """Compile every HIP source for gfx950 and link the C-ABI shared libraries; returns the model library's path.  ``out_name``: an
     A/B build of the model library alone under that name."""
@@ -76,6 +93,8 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), out_name=No
         _compile_and_link(CSRC_EVAL, EVAL_SOURCES, EVAL_LIBPATH, "", verbose, extra_flags)
     if out_name is None and (force or series_needs_build()):
         _compile_and_link(CSRC_SERIES, SERIES_SOURCES, SERIES_LIBPATH, "", verbose, extra_flags)
+    if out_name is None and (force or duration_needs_build()):
+        _compile_and_link(CSRC_DURATION, DURATION_SOURCES, DURATION_LIBPATH, "", verbose, extra_flags)
     global_out = LIBPATH if out_name is None else os.path.join(LIBDIR, out_name)
     if out_name is None and not force and not needs_build(global_out):
         return global_out
